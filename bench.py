@@ -12,6 +12,10 @@ One "step" = one complete penalty-SQP solve of the rank's whole shard starting f
 the state resident in HBM, followed (N > 1) by the RCCL all-gather of the 24-byte
 per-problem result records.  Reference solver defaults (solver.py:17-28,
 osqp_utils.py:10-15), reference quirks reproduced (parity mode).
+
+A plain run sets up, warms up, times the steps and prints the result line.  `--full` adds what the
+headline figure does not need: the CPU baselines and the aux lines that take runs of their own (12-DOF x 50,
+batch 4096, the object API).  `--dump-outputs DIR` writes the last timed step's results as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -259,6 +263,22 @@ def object_api_line(B, array_step_s):
             "python_f_calls": int(host_evals), "success_fraction": float(np.mean(oks))}
 
 
+def dump_outputs(path, arrays, cap=64 << 20):
+    """Write every per-problem array as float64 <path>/<name>.npy.  Row i of each is problem i (rank 0's shard starts at
+    problem 0).  Above `cap` bytes in all, a fixed seeded sample of the problems is kept, the same rows of every array,
+    and their indices go to sample_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > cap:
+        n = min(len(a) for a in arrays.values())
+        row_bytes = 8 + sum(a[0].nbytes for a in arrays.values())
+        keep = np.sort(np.random.default_rng(0).choice(n, min(n, cap // row_bytes), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sample_index"] = keep.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -290,18 +310,24 @@ def main():
                          "the default is weak scaling, --batch problems per GPU")
     ap.add_argument("--workload", choices=["7x20", "12x50"], default="7x20",
                     help="7x20 = BASELINE configs[2] (headline); 12x50 = configs[4] shape (structured global-memory tier)")
-    ap.add_argument("--cpu-problems", type=int, default=16, help="size of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the aux lines below (off: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-problems", type=int, default=16, help="with --full: size of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--aux-12x50", type=int, default=2048,
-                    help="batch of the 12-DOF x 50 line reported under aux in a default 7x20 run (0 = skip)")
-    ap.add_argument("--aux-b4096", type=int, default=1, help="also report a 4096-problem 7x20 step under aux (0 = skip)")
+                    help="with --full: batch of the 12-DOF x 50 line reported under aux in a 7x20 run (0 = skip)")
+    ap.add_argument("--aux-b4096", type=int, default=1, help="with --full: also report a 4096-problem 7x20 step under aux (0 = skip)")
     ap.add_argument("--aux-object-api", type=int, default=1,
-                    help="also solve the 1024 problems as 1024 Prob objects through solve_many, reported under aux (0 = skip)")
+                    help="with --full: also solve the 1024 problems as 1024 Prob objects through solve_many, reported under aux (0 = skip)")
     ap.add_argument("--intended", action="store_true",
                     help="disable reference quirks Q1/Q2 (NOT the headline number)")
     ap.add_argument("--beyond", action="store_true",
                     help="--intended plus the opt-in extensions: adaptive rho, warm-started QPs, at most 20 QPs "
                          "per problem (NOT the headline number, NOT parity mode)")
     args = ap.parse_args()
+    if not args.full:
+        args.cpu_problems = args.aux_12x50 = args.aux_b4096 = args.aux_object_api = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))          # nothing has touched the GPU yet
@@ -402,7 +428,7 @@ def main():
             elapsed = sd.max_over_ranks(elapsed)                  # device tensor under RCCL, host tensor under gloo
         return dict(dims=dims, B=B, total=total, steps=steps, elapsed=elapsed, sco_iters=sco_iters, admm_ms=admm_ms, wv=wv, per_rank=per_rank,
                     qp_launches=qp_launches, groups=groups, stage_ms=stage_ms / steps, it_proj=it_proj, it_pen=it_pen, qp_solves=qp_solves,
-                    success=float(np.mean(allrec["success"] != 0)))
+                    success=float(np.mean(allrec["success"] != 0)), res=res, records=allrec)
 
     def roofline(r, big):
         """Roofline block of the dominant kernel: algorithmic work of this rank's launches / their HIP-event time."""
@@ -487,6 +513,11 @@ def main():
     if big and args.cpu_problems == 16:
         args.cpu_problems = 0          # one 12x50 oracle solve takes minutes (tests/golden/make_big_oracle.py)
     r = run(args.workload, B, args.steps, args.warmup, args.intended, args.beyond)
+    if args.dump_outputs and rank == 0:
+        res = r["res"]
+        dump_outputs(args.dump_outputs, dict(
+            [(k, getattr(res, k)) for k in ("x", "success", "sqp_iters", "qp_solves", "admm_iters", "merit", "max_violation", "flags")] +
+            [("records_" + k, r["records"][k]) for k in r["records"].dtype.names]))
     aux12 = None
     if world == 1 and not big and not (args.intended or args.beyond) and args.aux_12x50 > 0:
         # BASELINE configs[4] shape on the structured global-memory tier: one step, reported under aux (a failure here
