@@ -262,6 +262,17 @@ void sco_sqp_default_params(sco_sqp_params *p);
                                   from first and second difference matrices, prob.py:88-104, 348-367): P gets its second
                                   super-diagonal block; weights via sco_sqp_load_acc_weights (0 until then); horizon >= 3 */
 
+#define SCO_FAM_FLAG_OBJ_BLOCK 512    /* OR-ed into SCO_FAM_STATE_PROGRAM with span 2 .. 4 and span * dof <= 16; exclusive with
+                                  SCO_FAM_FLAG_OBJ_PROGRAM and SCO_FAM_FLAG_EE_COST: one more program -- row index n_obstacles of
+                                  sco_sqp_load_program{,_steps}, SCO_OP_X < span * dof -- is a NON-QUADRATIC OBJECTIVE TERM
+                                  f(theta[t .. t+span-1], p) per constraint BLOCK, on the same Variable as the block's rows (a
+                                  transition cost: control effort, path length; Prob.add_obj_expr on a plain Expr over two or more
+                                  timesteps, prob.py:88-104).  The horizon - span + 1 terms read the block's parameters and are
+                                  convexified to degree 2 on every SQP iteration like SCO_FAM_FLAG_OBJ_PROGRAM; the Hessian of a
+                                  block fills its off-diagonal blocks of P too, so column (t, j) of the penalty QP's P holds the
+                                  dense band of rows max(0, t - span + 1) * dof .. t * dof + j (plus (t - 2, j) with
+                                  SCO_FAM_FLAG_ACC_COST and span 2), and overlapping blocks add up in block order */
+
 typedef struct sco_trajopt_desc {
   int batch;
   int dof;
@@ -322,7 +333,7 @@ int sco_sqp_load_quadratic(sco_sqp *h, const double *Q, const double *a, const d
  * pairs, the last one SCO_OP_END; consts[n_consts]; params[batch][n_params] (n_params may be 0).  There are R = n_obstacles
  * programs (the rows of a block: inequalities first, then the n_eq_rows equalities; SCO_OP_X addresses the span * dof numbers
  * of the block's state), with SCO_FAM_FLAG_OBJ_PROGRAM one more -- the objective term of a timestep, SCO_OP_X < dof --
- * and row_ptr[R] (or row_ptr[R + 1]) = n_words.  row_ptr is checked as a whole (first entry 0, strictly increasing, last =
+ * or with SCO_FAM_FLAG_OBJ_BLOCK one more -- the objective term of a block, SCO_OP_X < span * dof -- and row_ptr[R] (or row_ptr[R + 1]) = n_words.  row_ptr is checked as a whole (first entry 0, strictly increasing, last =
  * n_words) before any word is read through it, then every program (stack depth, operand indices, one result) before anything
  * is uploaded.  May be called again (new parameters per solve): the handle reuses its buffers. */
 int sco_sqp_load_program(sco_sqp *h, int n_words, const int *words, const int *row_ptr, int n_consts, const double *consts,

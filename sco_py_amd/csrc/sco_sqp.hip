@@ -88,9 +88,10 @@ struct SqpDev {
   // SCO_FAM_FLAG_EE_COST: non-quadratic objective term weight * ||ee(theta_t) - target||^2 per timestep, convexified to
   // degree 2 every SQP iteration (expr.py:143-153): oH = Hessian after the eigenvalue shift, oA, ob = the model's
   // linear and constant part; ppos = position in qp1's P values of entry (row (t, 0), column (t, j))
-  int cost;          // 1 = the arm's end-effector term, 2 = an objective PROGRAM (SCO_FAM_FLAG_OBJ_PROGRAM: program index R)
-  double *cw, *ctgt, *oH, *oA, *ob;   // [B], [B][2], [B][T][d*d], [B][T][d], [B][T]
-  const int *ppos;                    // [n_x]
+  int cost;          // 1 = the arm's end-effector term, 2 = an objective PROGRAM (SCO_FAM_FLAG_OBJ_PROGRAM: program index R),
+                     // 3 = an objective program per constraint BLOCK (SCO_FAM_FLAG_OBJ_BLOCK: program index R, state ds, NBt terms)
+  double *cw, *ctgt, *oH, *oA, *ob;   // [B], [B][2], [B][NO][dO*dO], [B][NO][dO], [B][NO] (NO, dO = T, d or NBt, ds)
+  const int *ppos;                    // [n_x]; cost 3: entry (r, c) of the dense band sits at ppos[c] + r
   const double *a0c, *a1c;      // constant parts of the A values of the projection / penalty QP (shared)
   double *vmax;                 // [B]
   double *jlo, *jhi;            // [B][d]
@@ -437,10 +438,11 @@ __device__ __forceinline__ double row_grad(const RowCtx &c, const RowRef &q, con
   return arm_row_grad(th, c.len, c.point_link[kp], c.point_frac[kp], c.obs[3 * o], c.obs[3 * o + 1], j);
 }
 // non-quadratic objective term of a timestep with up to two perturbed coordinates: the arm's end-effector term
-// (SCO_FAM_FLAG_EE_COST) or the objective program (SCO_FAM_FLAG_OBJ_PROGRAM: program index O)
+// (SCO_FAM_FLAG_EE_COST) or the objective program (SCO_FAM_FLAG_OBJ_PROGRAM / SCO_FAM_FLAG_OBJ_BLOCK: program index O; for a
+// block term `t` is the block and th its span * dof state)
 struct ObjCtx { int kind; const double *len; int d; double tx, ty, w; };
 __device__ __forceinline__ double obj_value(const ObjCtx &oc, const RowCtx &c, int t, const double *th, int pi, double hi, int pj, double hj) {
-  if (oc.kind == 2) return prog_eval(c, c.ppar + t * c.par_step, c.O - c.R1, th, pi, hi, pj, hj);
+  if (oc.kind >= 2) return prog_eval(c, c.ppar + t * c.par_step, c.O - c.R1, th, pi, hi, pj, hj);
   return arm_ee_cost(th, oc.len, oc.d, oc.tx, oc.ty, oc.w, pi, hi, pj, hj);
 }
 __device__ __forceinline__ double row_rhs(const RowCtx &c, const RowRef &q) { return q.eq == 1 ? c.target[q.r] : 0.0; }
@@ -583,6 +585,13 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_post_kernel(SqpDev s, QpDe
         const int t = col / d;
         const double wj = s.objw ? s.objw[(size_t)b * d + col % d] : 1.0;
         const double aj = s.accw ? s.accw[(size_t)b * d + col % d] : 0.0;
+        if (s.cost == 3) {                    // block terms: the dense band of rows max(0, t - S + 1) d .. col
+          if (s.acc && s.S == 2 && t > 1) Pv[pos++] = 2.0 * aj;
+          for (int r = (t - s.S + 1 > 0 ? t - s.S + 1 : 0) * d; r <= col; r++)
+            Pv[pos++] = r == col ? obj_p_diag(t, s.T, wj, aj) : r == col - d ? obj_p_off1(t, s.T, wj, aj) :
+                        (s.acc && r == col - 2 * d) ? 2.0 * aj : 0.0;
+          continue;
+        }
         if (s.acc && t > 1) Pv[pos++] = 2.0 * aj;                            // ((t - 2, j), (t, j)): first x last of window t - 2
         if (t > 0) Pv[pos++] = obj_p_off1(t, s.T, wj, aj);
         if (s.cost) for (int i = 0; i < col % d; i++) Pv[pos++] = 0.0;
@@ -643,6 +652,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
   __shared__ double of0[260];           // f of the non-quadratic objective terms at the convexification point
   const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, O = s.O, n = s.n, m = s.m;
   const int ds = s.ds, NBt = s.NBt;             // state dimension of a block, number of timestep blocks
+  const int NO = s.cost == 3 ? NBt : T;         // objective terms: one per timestep, or one per block (cost 3)
   const RowLay L{T, NBt, R, s.Req};
   double *x = s.x + (size_t)b * n_x, *xs = s.x_saved + (size_t)b * n_x;
   const double *len = s.link_len + (size_t)b * d;
@@ -752,12 +762,14 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
     double *qv = q1.q + (size_t)b * n;
     for (int i = tid; i < s.n_slack; i += SCO_BLOCK) qv[n_x + i] = slack_cost;   // prob.py:424-426
     if (s.cost) {
-      // ---- non-quadratic objective terms: Expr.convexify(degree 2) (expr.py:143-153) per timestep block
+      // ---- non-quadratic objective terms: Expr.convexify(degree 2) (expr.py:143-153) per timestep block, or per constraint
+      // block of S timesteps (cost 3: NO = NBt terms on dO = ds numbers; block t's state starts at x[t d] as well)
       const ObjCtx oc{s.cost, len, d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]};
-      double *oH = s.oH + (size_t)b * T * d * d, *oA = s.oA + (size_t)b * T * d, *ob = s.ob + (size_t)b * T;
+      const int dO = s.cost == 3 ? ds : d;
+      double *oH = s.oH + (size_t)b * NO * dO * dO, *oA = s.oA + (size_t)b * NO * dO, *ob = s.ob + (size_t)b * NO;
       // f(x), memoised on the rounded point like every Expr.eval (expr.py:34-41); the term shares the point history of
-      // its timestep's constraint block (same Variable, same evaluation points): its value is the block's last column
-      for (int t = tid; t < T; t += SCO_BLOCK) {
+      // its constraint block (same Variable, same evaluation points): its value is the block's last column
+      for (int t = tid; t < NO; t += SCO_BLOCK) {
         double f;
         if (ev_hit[t] >= 0) f = hval[((size_t)t * H + ev_hit[t]) * RM + (RM - 1)];
         else {
@@ -768,11 +780,11 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
       }
       __syncthreads();
       // numeric Hessian (expr.py:102-109; second central differences on the halving ladder, Richardson: numdiff.py)
-      const int npair = d * (d + 1) / 2;
-      for (int e = tid; e < T * npair; e += SCO_BLOCK) {
+      const int npair = dO * (dO + 1) / 2;
+      for (int e = tid; e < NO * npair; e += SCO_BLOCK) {
         const int t = e / npair;
         int k = e % npair, i = 0;
-        while (k >= d - i) { k -= d - i; i++; }
+        while (k >= dO - i) { k -= dO - i; i++; }
         const int j = i + k;
         const double *th = x + t * d;
         const double si = FD_BASE * fmax(1.0, fabs(th[i])), sj = FD_BASE * fmax(1.0, fabs(th[j]));
@@ -793,11 +805,11 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
           }
         }
         const double hv = richardson(tab);
-        oH[(size_t)t * d * d + i * d + j] = hv; oH[(size_t)t * d * d + j * d + i] = hv;
+        oH[(size_t)t * dO * dO + i * dO + j] = hv; oH[(size_t)t * dO * dO + j * dO + i] = hv;
       }
       // numeric gradient (expr.py:61-69), parked in oA until the block's thread turns it into the model's A
-      for (int e = tid; e < T * d; e += SCO_BLOCK) {
-        const int t = e / d, j = e % d;
+      for (int e = tid; e < NO * dO; e += SCO_BLOCK) {
+        const int t = e / dO, j = e % dO;
         const double *th = x + t * d;
         const double h0 = FD_BASE * fmax(1.0, fabs(th[j]));
         double tab[FD_LEVELS];
@@ -810,24 +822,49 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
       }
       __syncthreads();
       // eigenvalue shift, then Q = H, A = g - x'H, b = 1/2 x'Hx - g.x + f (expr.py:145-152)
-      for (int t = tid; t < T; t += SCO_BLOCK) {
-        double *Ht = oH + (size_t)t * d * d;
+      for (int t = tid; t < NO; t += SCO_BLOCK) {
+        double *Ht = oH + (size_t)t * dO * dO;
         const double *th = x + t * d;
-        const double lam = min_eig_jacobi(Ht, d);
-        if (lam < 0.0) for (int i = 0; i < d; i++) Ht[i * d + i] -= lam;
+        const double lam = min_eig_jacobi(Ht, dO);
+        if (lam < 0.0) for (int i = 0; i < dO; i++) Ht[i * dO + i] -= lam;
         double xHx = 0.0, gx = 0.0, g[OBJ_DMAX], xH[OBJ_DMAX];
-        for (int j = 0; j < d; j++) {
-          g[j] = oA[t * d + j];
+        for (int j = 0; j < dO; j++) {
+          g[j] = oA[t * dO + j];
           double acc = 0.0;
-          for (int i = 0; i < d; i++) acc += th[i] * Ht[i * d + j];
+          for (int i = 0; i < dO; i++) acc += th[i] * Ht[i * dO + j];
           xH[j] = acc;
         }
-        for (int j = 0; j < d; j++) { xHx += xH[j] * th[j]; gx += g[j] * th[j]; oA[t * d + j] = g[j] - xH[j]; }
+        for (int j = 0; j < dO; j++) { xHx += xH[j] * th[j]; gx += g[j] * th[j]; oA[t * dO + j] = g[j] - xH[j]; }
         ob[t] = (0.5 * xHx - gx) + of0[t];
       }
       __syncthreads();
       // QuadExpr lowering (prob.py:348-367; osqp_utils.py:153-163): Q into the upper triangle of P, A into q
       double *Pv = q1.Pval + (size_t)b * q1.nnzP;
+      if (s.cost == 3) {
+        // blocks overlap: every entry of the band is written by one thread, which adds, in the reference's order, the
+        // smoothing QuadExpr first, then each covering block's Q in block order -- an off-diagonal pair as its two halves
+        // 0.5 Q_ij + 0.5 Q_ji, the diagonal whole (osqp_utils.py:153-163); q likewise (osqp_utils.py:146-148)
+        const int S = s.S;
+        for (int e = tid; e < n_x * ds; e += SCO_BLOCK) {
+          const int c = e / ds, tc = c / d, j = c % d, tlo = tc - S + 1 > 0 ? tc - S + 1 : 0, r = tlo * d + e % ds;
+          if (r > c) continue;
+          const int thi = r / d < NBt - 1 ? r / d : NBt - 1;
+          const double wj = s.objw ? s.objw[(size_t)b * d + j] : 1.0, aj = s.accw ? s.accw[(size_t)b * d + j] : 0.0;
+          double v = r == c ? obj_p_diag(tc, T, wj, aj) : r == c - d ? obj_p_off1(tc, T, wj, aj) : (s.acc && r == c - 2 * d) ? 2.0 * aj : 0.0;
+          for (int t = tlo; t <= thi; t++) {
+            const double h = oH[(size_t)t * ds * ds + (r - t * d) * ds + (c - t * d)];
+            if (r == c) v += h;
+            else { v += 0.5 * h; v += 0.5 * h; }
+          }
+          Pv[s.ppos[c] + r] = v;
+        }
+        for (int i = tid; i < n_x; i += SCO_BLOCK) {
+          const int ti = i / d, thi = ti < NBt - 1 ? ti : NBt - 1;
+          double acc = 0.0;
+          for (int t = ti - S + 1 > 0 ? ti - S + 1 : 0; t <= thi; t++) acc += oA[t * ds + (i - t * d)];
+          qv[i] = acc;
+        }
+      } else {
       for (int e = tid; e < T * npair; e += SCO_BLOCK) {
         const int t = e / npair;
         int k = e % npair, i = 0;
@@ -837,9 +874,10 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
         Pv[s.ppos[t * d + j] + i] = base + oH[(size_t)t * d * d + i * d + j];
       }
       for (int e = tid; e < n_x; e += SCO_BLOCK) qv[e] = oA[e];
+      }
     }
     // S7: merit at the convexification point (prob.py:571-579), S4 prerequisite: save
-    double v[2] = {traj_obj_partial(x, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr) + ((s.cost && tid < T) ? of0[tid] : 0.0), 0.0};
+    double v[2] = {traj_obj_partial(x, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr) + ((s.cost && tid < NO) ? of0[tid] : 0.0), 0.0};
     for (int e = tid; e < m_nl; e += SCO_BLOCK) {
       const RowRef q = row_ref(e, L);
       v[1] += row_viol(q, gs[e] - row_rhs(rc, q));
@@ -936,14 +974,15 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
   //    objective terms at the new point (prob.py:571-573), max violation at the saved point
   double v[6] = {traj_obj_partial(xq, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr), 0.0, 0.0, 0.0, 0.0, 0.0};
   if (s.cost) {
-    const double *oH = s.oH + (size_t)b * T * d * d, *oA = s.oA + (size_t)b * T * d, *ob = s.ob + (size_t)b * T;
-    for (int t = tid; t < T; t += SCO_BLOCK) {
-      const double *th = xq + t * d, *Ht = oH + (size_t)t * d * d;
+    const int NO = s.cost == 3 ? NBt : T, dO = s.cost == 3 ? ds : d;     // per timestep, or per block (cost 3)
+    const double *oH = s.oH + (size_t)b * NO * dO * dO, *oA = s.oA + (size_t)b * NO * dO, *ob = s.ob + (size_t)b * NO;
+    for (int t = tid; t < NO; t += SCO_BLOCK) {
+      const double *th = xq + t * d, *Ht = oH + (size_t)t * dO * dO;
       double xHx = 0.0, ax = 0.0;
-      for (int i = 0; i < d; i++) {
+      for (int i = 0; i < dO; i++) {
         double acc = 0.0;
-        for (int j = 0; j < d; j++) acc += Ht[i * d + j] * th[j];
-        xHx += th[i] * acc; ax += oA[t * d + i] * th[i];
+        for (int j = 0; j < dO; j++) acc += Ht[i * dO + j] * th[j];
+        xHx += th[i] * acc; ax += oA[t * dO + i] * th[i];
       }
       v[3] += (0.5 * xHx + ax) + ob[t];                        // QuadExpr.eval (expr.py:205-206)
       double f;
@@ -1090,7 +1129,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_final_kernel(SqpDev s, double *
   const RowLay L{T, s.NBt, R, s.Req};
   double v[3] = {traj_obj_partial(x, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr), 0.0, 0.0};
   if (s.cost)
-    for (int t = tid; t < T; t += SCO_BLOCK)
+    for (int t = tid; t < (s.cost == 3 ? s.NBt : T); t += SCO_BLOCK)
       v[0] += obj_value(ObjCtx{s.cost, len, d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]}, rc, t, x + t * d, -1, 0.0, -1, 0.0);
   for (int e = tid; e < s.m_nl; e += SCO_BLOCK) {
     const RowRef q = row_ref(e, L);
@@ -1149,7 +1188,7 @@ extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int
   const int fam = desc->family & 15, span = desc->span > 0 ? desc->span : 1;
   const bool statefam = fam == SCO_FAM_STATE_QUADRATIC || fam == SCO_FAM_STATE_PROGRAM;
   if (desc->batch <= 0 || desc->dof <= 0 || desc->horizon < 2 || desc->n_points <= 0 || desc->n_obstacles <= 0 ||
-      desc->horizon > 256 || (desc->family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_ACC_COST)) ||
+      desc->horizon > 256 || (desc->family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_ACC_COST | SCO_FAM_FLAG_OBJ_BLOCK)) ||
       ((desc->family & SCO_FAM_FLAG_EE_COST) && desc->dof > OBJ_DMAX) || ((desc->family & SCO_FAM_FLAG_ACC_COST) && desc->horizon < 3) ||
       (fam != SCO_FAM_ARM_CIRCLES && fam != SCO_FAM_ARM_REACH && fam != SCO_FAM_POINT_CIRCLES && !statefam) ||
       (fam == SCO_FAM_POINT_CIRCLES && (desc->n_points != 1 || desc->dof < 2 || (desc->family & SCO_FAM_FLAG_EE_COST))) ||
@@ -1159,7 +1198,10 @@ extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int
       desc->span < 0 || desc->span > 4 || desc->n_eq_rows < 0 || desc->n_eq_rows > desc->n_obstacles ||
       (span > 1 && fam != SCO_FAM_STATE_PROGRAM) || (desc->n_eq_rows > 0 && !statefam) ||
       (fam == SCO_FAM_STATE_PROGRAM && (span * desc->dof > SCO_STATE_MAX || span >= desc->horizon)) ||
-      ((desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) && (fam != SCO_FAM_STATE_PROGRAM || span != 1 || desc->dof > OBJ_DMAX))) {
+      ((desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) && (fam != SCO_FAM_STATE_PROGRAM || span != 1 || desc->dof > OBJ_DMAX)) ||
+      // an objective program per constraint block: span 2 .. 4, the block's state fits the per-thread eigenvalue sweep
+      ((desc->family & SCO_FAM_FLAG_OBJ_BLOCK) && (fam != SCO_FAM_STATE_PROGRAM || span < 2 || span * desc->dof > OBJ_DMAX ||
+                                                   (desc->family & (SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_EE_COST))))) {
     sco_set_error("sco_sqp_create: bad descriptor"); return SCO_ERR_ARG;
   }
   int ndev = 0;
@@ -1198,7 +1240,8 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
   const int B = desc->batch, d = desc->dof, T = desc->horizon, K = desc->n_points, O = desc->n_obstacles;
   const bool reach = (desc->family & 15) == SCO_FAM_ARM_REACH, vel = (desc->family & SCO_FAM_FLAG_VEL_LIMITS) != 0;
   const bool jl = (desc->family & SCO_FAM_FLAG_JOINT_LIMITS) != 0;
-  const bool cost = (desc->family & (SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM)) != 0;
+  const bool cost = (desc->family & (SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_OBJ_BLOCK)) != 0;
+  const bool oblk = (desc->family & SCO_FAM_FLAG_OBJ_BLOCK) != 0;
   const bool acc = (desc->family & SCO_FAM_FLAG_ACC_COST) != 0;
   const int NE = reach ? 2 : 0;                  // equality rows (end-effector x, y) on the last timestep
   const int S = desc->span > 0 ? desc->span : 1, ds = S * d, NBt = T - S + 1, Req = desc->n_eq_rows;
@@ -1255,7 +1298,14 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
     std::vector<int> Pp(n + 1), Pi, Ap(n + 1), Ai;
     for (int col = 0; col < n; col++) {
       Pp[col] = (int)Pi.size();
-      if (col < n_x) {
+      if (col < n_x && oblk) {
+        // block terms (SCO_FAM_FLAG_OBJ_BLOCK): a block's Hessian couples all its S timesteps, so column (t, j) holds the
+        // dense band of rows max(0, t - S + 1) d .. col -- with the acceleration term's (t - 2, j) in front when S = 2
+        const int t = col / d, r0 = std::max(0, t - S + 1) * d;
+        if (acc && S == 2 && t > 1) Pi.push_back(col - 2 * d);
+        ppos[col] = (int)Pi.size() - r0;           // entry (r, col) sits at ppos + r
+        for (int r = r0; r <= col; r++) Pi.push_back(r);
+      } else if (col < n_x) {
         if (acc && col / d > 1) Pi.push_back(col - 2 * d);       // acceleration term (r04): second super-diagonal block
         if (col / d > 0) Pi.push_back(col - d);
         ppos[col] = (int)Pi.size();
@@ -1313,7 +1363,7 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
   s.S = S; s.ds = ds; s.NBt = NBt; s.Req = Req;
   s.m_gen = m_gen; s.nnz_gen = nnz_gen;
   s.acc = acc ? 1 : 0;
-  s.m_pin = m_pin; s.m_vel = m_vel; s.m_jl = m_jl; s.cost = (desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) ? 2 : cost ? 1 : 0;
+  s.m_pin = m_pin; s.m_vel = m_vel; s.m_jl = m_jl; s.cost = oblk ? 3 : (desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) ? 2 : cost ? 1 : 0;
   int rc = 0;
 #define AL(f, cnt) if ((rc = sq_alloc(h, (cnt), &s.f))) return rc;
   AL(x0, (size_t)B * n_x) AL(start, (size_t)B * d) AL(goal, (size_t)B * d) AL(link_len, (size_t)B * d)
@@ -1330,7 +1380,10 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
   AL(cJ, (size_t)B * s.NB * s.HC * s.RM * ds) AL(cb, (size_t)B * s.NB * s.HC * s.RM) AL(hn, (size_t)B * s.NB)
   AL(cn, (size_t)B * s.NB)
   AL(cw, (size_t)B) AL(ctgt, (size_t)B * 2)
-  AL(oH, cost ? (size_t)B * T * d * d : 1) AL(oA, cost ? (size_t)B * T * d : 1) AL(ob, cost ? (size_t)B * T : 1)
+  {
+    const size_t NO = oblk ? NBt : T, dO = oblk ? ds : d;     // objective terms and their state
+    AL(oH, cost ? (size_t)B * NO * dO * dO : 1) AL(oA, cost ? (size_t)B * NO * dO : 1) AL(ob, cost ? (size_t)B * NO : 1)
+  }
 #undef AL
   { int *p; if ((rc = sq_alloc(h, (size_t)n_x, &p))) return rc; s.ppos = p;
     SCO_HIP(hipMemcpy(p, ppos.data(), n_x * sizeof(int), hipMemcpyHostToDevice)); }
@@ -1487,8 +1540,8 @@ static int load_program_impl(sco_sqp *h, int n_words, const int *words, const in
   }
   if ((h->desc.family & 15) != SCO_FAM_STATE_PROGRAM) { sco_set_error("sco_sqp_load_program: family has no row programs"); return SCO_ERR_ARG; }
   if (!h->loaded) { sco_set_error("sco_sqp_load_program: call sco_sqp_load first"); return SCO_ERR_STATE; }
-  // the rows of a block, then (SCO_FAM_FLAG_OBJ_PROGRAM) the objective term of a timestep
-  const int R = h->d.O - h->d.R1 + (h->d.cost == 2 ? 1 : 0), ds = h->d.ds;       // (r04: R1 leading rows of a block are circle rows)
+  // the rows of a block, then (SCO_FAM_FLAG_OBJ_PROGRAM) the objective term of a timestep or (SCO_FAM_FLAG_OBJ_BLOCK) of a block
+  const int R = h->d.O - h->d.R1 + (h->d.cost >= 2 ? 1 : 0), ds = h->d.ds;       // (r04: R1 leading rows of a block are circle rows)
   if (n_words <= 0 || n_consts < 0 || n_params < 0) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
   // the whole of row_ptr is checked BEFORE any word is read through it: 0 = first entry, strictly increasing, last = n_words
   if (row_ptr[0] != 0) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
@@ -1500,7 +1553,7 @@ static int load_program_impl(sco_sqp *h, int n_words, const int *words, const in
     if (words[2 * (row_ptr[r + 1] - 1)] != SCO_OP_END) {
       sco_set_error("sco_sqp_load_program: a row's program must end with SCO_OP_END"); return SCO_ERR_ARG;
     }
-    const int nx = r < h->d.O - h->d.R1 ? ds : h->d.d;      // the objective term sees one timestep
+    const int nx = (r < h->d.O - h->d.R1 || h->d.cost == 3) ? ds : h->d.d;      // the objective term sees one timestep (a block's: ds)
     int sp = 0;
     for (int w = row_ptr[r]; w < row_ptr[r + 1] - 1; w++) {
       const int op = words[2 * w], arg = words[2 * w + 1];

@@ -151,3 +151,19 @@ class ProgramObjExpr(DeviceExpr):
         self.params = _f64(params).ravel()
         super(ProgramObjExpr, self).__init__(
             lambda x: np.array([[program.evaluate(x.ravel(), self.params, rows=[program.n_rows])[0]]]))
+
+
+class ProgramBlockObjExpr(DeviceExpr):
+    """SCO_FAM_FLAG_OBJ_BLOCK: the objective program of a ``rowexpr.Program`` (``compile_rows(..., block_objective=)``)
+    as the non-quadratic objective term of one constraint block -- bind it to the block's own Variable (the ``span``
+    timesteps t .. t + span - 1, (span * dof, 1)) with the block's parameter vector: a transition cost such as control
+    effort or path length."""
+    kind = "program_block_obj"
+    role = "objective"
+
+    def __init__(self, program, params=()):
+        assert program.block_objective
+        self.program = program
+        self.params = _f64(params).ravel()
+        super(ProgramBlockObjExpr, self).__init__(
+            lambda x: np.array([[program.evaluate(x.ravel(), self.params, rows=[program.n_rows])[0]]]))

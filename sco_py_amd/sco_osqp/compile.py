@@ -18,7 +18,8 @@ What is read and what it must look like (each test names the reference behaviour
 * ``Variable`` objects: all hold values, agree on them, and every atom is held by the same number of Variables apart
   from the constraint blocks covering it -- the projection QP adds one (x_i - x0_i)^2 per holder (prob.py:381-404);
 * objective: one ``QuadExpr`` sum_t |x_{t+1} - x_t|^2 on the whole trajectory (prob.py:348-367), optionally one
-  non-quadratic ``DeviceExpr`` objective term per timestep (prob.py:88-104);
+  non-quadratic ``DeviceExpr`` objective term per timestep (prob.py:88-104), or, for a program with a block objective,
+  one ``ProgramBlockObjExpr`` per constraint block on that block's own Variable (SCO_FAM_FLAG_OBJ_BLOCK);
 * affine rows in the order they were added (``_osqp_lin_cnt_exprs``, prob.py:317-346): start pin, goal pin, velocity
   limits, joint limits; r04: whatever follows them is taken as general affine rows (equalities and upper bounds over the
   trajectory atoms) -- a shared sparsity pattern per device batch, coefficients and right-hand sides per problem;
@@ -28,6 +29,7 @@ What is read and what it must look like (each test names the reference behaviour
 import numpy as np
 
 from .. import devexpr as dx
+from .. import rowexpr as rx
 from .. import workloads as wl
 from .. import expr as ex
 
@@ -287,7 +289,23 @@ def _compile(prob):
     if has_acc:
         pr["acc_w"] = aw
     nq = list(prob._nonquad_obj_exprs)
-    if nq:
+    if nq and fam == "program" and pr["row_program"].block_objective:
+        # SCO_FAM_FLAG_OBJ_BLOCK: one ProgramBlockObjExpr per constraint block, on that block's own Variable, with the rows'
+        # program and the block's parameters
+        if span * d > rx.OBJ_DMAX:
+            _no("block objective terms on more than %d numbers (span * dof)" % rx.OBJ_DMAX)
+        if len(nq) != n_blocks:
+            _no("block objective terms: one per constraint block")
+        rp = pr["row_params"]
+        for t, be in enumerate(nq):
+            if not isinstance(be.expr, dx.ProgramBlockObjExpr):
+                _no("block objective terms are not ProgramBlockObjExpr")
+            if be.var is not blocks[t][0].var:
+                _no("a block objective term is not on its constraint block's Variable")
+            if be.expr.program is not pr["row_program"] or not _same(be.expr.params, rp[t] if np.ndim(rp) == 2 else rp):
+                _no("a block objective term has another program than the rows, or other parameters than its block's")
+        key_fam = key_fam + ("block_obj",)
+    elif nq:
         if len(nq) != T:
             _no("objective terms: one per timestep")
         o0 = nq[0].expr
@@ -308,7 +326,7 @@ def _compile(prob):
                 _no("the objective program is not the constraint rows' program (or its parameters are not its timestep's)")
         else:
             _no("this objective term does not go with the %s family" % fam)
-    elif fam == "program" and pr["row_program"].objective:
+    elif fam == "program" and (pr["row_program"].objective or pr["row_program"].block_objective):
         _no("the program carries an objective term the Prob does not use")
 
     # ---- affine rows ---------------------------------------------------------------------------------------------

@@ -288,7 +288,20 @@ def variant_program(variant, d):
     key = (variant, d)
     if key in _PROGRAMS:
         return _PROGRAMS[key]
-    from .rowexpr import X, P, sin, cos, sqrt, exp, compile_rows
+    from .rowexpr import compile_rows
+    v = variant_rows(variant, d)
+    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], objective=v["objective"])
+    if variant == "attract":
+        assert prog.n_rows == corridor_program(d).n_rows
+    _PROGRAMS[key] = prog
+    return prog
+
+
+def variant_rows(variant, d):
+    """The expressions behind variant_program(variant, d): dict(rows=, eq_rows=, span=, objective=) -- fresh expression trees
+    that compile_rows turns into that program (and that block_obj_program compiles again with a block objective term)."""
+    from .rowexpr import X, P, sin, cos, sqrt, exp
+    eq, span, objective = [], 1, None
     if variant == "sweep":
         rows = []
         mx, my = 0.5 * (X(0) + X(d)), 0.5 * (X(1) + X(d + 1))
@@ -297,7 +310,7 @@ def variant_program(variant, d):
             dx, dy = mx - P(3 * o), my - P(3 * o + 1)
             rows.append(P(3 * o + 2) * (1.0 + P(6) * step2) - sqrt(dx ** 2 + dy ** 2 + 1e-12))
         rows.append(step2 - (P(7) + P(8) * my) ** 2)                  # shorter steps where the midpoint is low
-        prog = compile_rows(rows, span=2)
+        span = 2
     elif variant == "accel":
         rows = []
         for o in range(2):
@@ -305,7 +318,7 @@ def variant_program(variant, d):
             rows.append(P(3 * o + 2) - sqrt(dx ** 2 + dy ** 2 + 1e-12))
         ax, ay = X(0) - 2.0 * X(d) + X(2 * d), X(1) - 2.0 * X(d + 1) + X(2 * d + 1)
         rows.append(ax ** 2 + ay ** 2 - (P(6) * (1.0 + P(7) * X(d + 1))) ** 2)
-        prog = compile_rows(rows, span=3)
+        span = 3
     elif variant == "jerk":
         jx, jy = X(3 * d) - 3.0 * X(2 * d) + 3.0 * X(d) - X(0), X(3 * d + 1) - 3.0 * X(2 * d + 1) + 3.0 * X(d + 1) - X(1)
         cx, cy = 0.25 * (X(0) + X(d) + X(2 * d) + X(3 * d)), 0.25 * (X(1) + X(d + 1) + X(2 * d + 1) + X(3 * d + 1))
@@ -313,13 +326,13 @@ def variant_program(variant, d):
         rows = [P(2) * (1.0 + P(7) * chord2) - sqrt((cx - P(0)) ** 2 + (cy - P(1)) ** 2 + 1e-12),
                 P(5) - sqrt((X(d) - P(3)) ** 2 + (X(d + 1) - P(4)) ** 2 + 1e-12),
                 jx ** 2 + jy ** 2 - P(6) ** 2]
-        prog = compile_rows(rows, span=4)
+        span = 4
     elif variant == "dynamics":
         assert d == 3
-        ineq = [P(3) - sqrt((X(0) - P(1)) ** 2 + (X(1) - P(2)) ** 2 + 1e-12),            # keep-out disc on x_t
+        rows = [P(3) - sqrt((X(0) - P(1)) ** 2 + (X(1) - P(2)) ** 2 + 1e-12),            # keep-out disc on x_t
                 (X(5) - X(2)) ** 2 - P(5) ** 2]                                            # turn-rate limit
         eq = [X(3) - X(0) - P(0) * cos(X(2)), X(4) - X(1) - P(0) * sin(X(2))]             # unicycle step, speed p[0]
-        prog = compile_rows(ineq, eq_rows=eq, span=2)
+        span = 2
     elif variant == "curve":
         assert d == 3
         rows = []
@@ -328,9 +341,8 @@ def variant_program(variant, d):
             dx, dy = X(0) - cx, X(1) - cy
             dist = sqrt(dx ** 2 + dy ** 2 + 1e-12)
             rows.append(rad * (1.0 + rip * (dx / dist) * (dy / dist)) - dist)
-        prog = compile_rows(rows, eq_rows=[X(2) - P(8) * sin(P(9) * X(0))])
+        eq = [X(2) - P(8) * sin(P(9) * X(0))]
     elif variant == "attract":
-        base = corridor_program(d)
         # (rebuild the corridor rows as expressions: compile_rows wants Nodes, so the rows are written out again)
         rows = []
         for o in range(2):
@@ -342,13 +354,10 @@ def variant_program(variant, d):
         rows.append(P(11) - 0.5 * exp(-((X(0) - P(12)) ** 2) * 4.0) - X(1))
         if d > 2:
             rows[-1] = rows[-1] + 0.05 * cos(X(2))
-        well = -(P(13) * exp(-((X(0) - P(14)) ** 2 + (X(1) - P(15)) ** 2) / 0.18))
-        prog = compile_rows(rows, objective=well)
-        assert prog.n_rows == base.n_rows
+        objective = -(P(13) * exp(-((X(0) - P(14)) ** 2 + (X(1) - P(15)) ** 2) / 0.18))
     else:
         raise ValueError("unknown program variant %r" % (variant,))
-    _PROGRAMS[key] = prog
-    return prog
+    return dict(rows=rows, eq_rows=eq, span=span, objective=objective)
 
 
 def make_program_problem(i, d=2, T=20, noise=0.03, groups=None, vel_limit=None, joint_limit=None, variant=None):
@@ -455,6 +464,90 @@ def make_program_variant(i, variant, d=2, T=12, noise=0.03, groups=None, vel_lim
     return out
 
 
+def block_obj_program(kind, d):
+    """Programs of the block-objective workloads (SCO_FAM_FLAG_OBJ_BLOCK): the rows of a variant plus ONE non-quadratic
+    objective term per block, compiled once per (kind, dof).  The term's parameters follow the rows' (n = the variant's
+    parameter count):
+
+    "effort"   span 2, dof = 3, the "dynamics" rows, and the unicycle's control effort
+               p[n] (dx cos(phi) + dy sin(phi))^2 + p[n + 1] dphi^2 (squared speed along the heading, squared turn rate)
+               plus a Gaussian well -p[n + 2] exp(-|m - g|^2 / 0.08) on the step midpoint m around g = p[n + 3 : n + 5]
+               (non-convex away from g: the eigenvalue shift acts);
+    "ee-path"  span 2, dof <= 8, the "sweep" rows, and the planar end-effector step length p[n] |ee(theta_t+1) - ee(theta_t)|^2
+               of an arm with links of length 1 / dof (ee = sum_i l (cos, sin)(theta_0 + .. + theta_i));
+    "smooth3"  span 3, dof >= 2, the "accel" rows, and a robust (pseudo-Huber) cost of the second difference a of the window,
+               p[n] sqrt(1 + p[n + 1] |a|^2), plus a Gaussian well -p[n + 2] exp(-|x_t+1 - g|^2 / 0.08) on the middle point
+               around g = p[n + 3 : n + 5]."""
+    key = ("block_obj", kind, d)
+    if key in _PROGRAMS:
+        return _PROGRAMS[key]
+    from .rowexpr import X, P, sin, cos, sqrt, exp, compile_rows
+    if kind == "effort":
+        v, n = variant_rows("dynamics", d), 6
+        dx, dy, dphi = X(3) - X(0), X(4) - X(1), X(5) - X(2)
+        mx, my = 0.5 * (X(0) + X(3)), 0.5 * (X(1) + X(4))
+        term = P(n) * (dx * cos(X(2)) + dy * sin(X(2))) ** 2 + P(n + 1) * dphi ** 2 - \
+            P(n + 2) * exp(-((mx - P(n + 3)) ** 2 + (my - P(n + 4)) ** 2) / 0.08)
+    elif kind == "ee-path":
+        v, n = variant_rows("sweep", d), 9
+        ln = 1.0 / d
+
+        def ee(off):
+            phi, ex, ey = None, None, None
+            for k in range(d):
+                phi = X(off + k) if phi is None else phi + X(off + k)
+                ex = ln * cos(phi) if ex is None else ex + ln * cos(phi)
+                ey = ln * sin(phi) if ey is None else ey + ln * sin(phi)
+            return ex, ey
+        (ax, ay), (bx, by) = ee(0), ee(d)
+        term = P(n) * ((bx - ax) ** 2 + (by - ay) ** 2)
+    elif kind == "smooth3":
+        v, n = variant_rows("accel", d), 8
+        ax, ay = X(0) - 2.0 * X(d) + X(2 * d), X(1) - 2.0 * X(d + 1) + X(2 * d + 1)
+        term = P(n) * sqrt(1.0 + P(n + 1) * (ax ** 2 + ay ** 2)) - \
+            P(n + 2) * exp(-((X(d) - P(n + 3)) ** 2 + (X(d + 1) - P(n + 4)) ** 2) / 0.08)
+    else:
+        raise ValueError("unknown block-objective workload %r" % (kind,))
+    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], block_objective=term, dof=d)
+    _PROGRAMS[key] = prog
+    return prog
+
+
+BLOCK_OBJ = {"effort": ("dynamics", 3, 12), "ee-path": ("sweep", 7, 20), "smooth3": ("accel", 2, 10)}
+
+
+def make_block_obj_problem(i, kind, T=None, d=None, **kw):
+    """Seeded problem i of a block-objective workload (block_obj_program): the problem of the underlying variant ("effort":
+    "dynamics" at dof 3, T = 12; "ee-path": "sweep" at dof 7, T = 20; "smooth3": "accel" at dof 2, T = 10) unchanged, plus the
+    term's parameters from a generator of their own, appended to every parameter vector.  ``kw`` goes to make_problem
+    (obj_weights, per_step, acc_weights, vel_limit, groups, ...)."""
+    if kind not in BLOCK_OBJ:
+        raise ValueError("unknown block-objective workload %r" % (kind,))
+    if kw.get("circles"):
+        raise ValueError("circles: program family with blocks on one timestep (the block-objective workloads have span >= 2)")
+    variant, d0, T0 = BLOCK_OBJ[kind]
+    d = d0 if d is None else int(d)
+    T = T0 if T is None else int(T)
+    out = make_problem(i, program=True, variant=variant, d=d, T=T, **kw)
+    rng = np.random.default_rng(8800 + 31 * sorted(BLOCK_OBJ).index(kind) + 101 * i)
+    if kind == "ee-path":
+        extra = np.array([rng.uniform(0.5, 2.0)])
+    else:
+        a = rng.uniform(0.3, 0.7)
+        g = (1 - a) * out["start"][:2] + a * out["goal"][:2] + 0.1 * rng.standard_normal(2)
+        if kind == "effort":
+            extra = np.array([rng.uniform(0.02, 0.1), rng.uniform(0.01, 0.05), rng.uniform(0.005, 0.02), g[0], g[1]])
+        else:
+            extra = np.array([rng.uniform(0.05, 0.2), rng.uniform(5.0, 20.0), rng.uniform(0.005, 0.02), g[0], g[1]])
+    par = np.asarray(out["row_params"], dtype=np.float64)
+    if par.ndim == 2:
+        out["row_params"] = np.concatenate([par, np.broadcast_to(extra, (par.shape[0], extra.shape[0]))], axis=1)
+    else:
+        out["row_params"] = np.concatenate([par, extra])
+    out["row_program"] = block_obj_program(kind, d)
+    return out
+
+
 def general_rows(i, d, T, start, goal):
     """r04: GENERAL affine rows of problem i (prob.add_cnt_expr(BoundExpr(LEqExpr / EqExpr(AffExpr(A, 0), rhs), traj)), prob.py:126-131,
     317-346): the pattern depends on (d, T) only, coefficients and right-hand sides on the problem.  Inequalities first:
@@ -479,13 +572,18 @@ def general_rows(i, d, T, start, goal):
     return dict(A=np.array(rows), rhs=np.array(rhs), is_eq=np.array(eq, dtype=np.int32))
 
 
-def make_problem(i, obj_weights=False, per_step=False, lin_rows=False, circles=0, acc_weights=False, **kw):
+def make_problem(i, obj_weights=False, per_step=False, lin_rows=False, circles=0, acc_weights=False, block_obj=None, **kw):
     """Seeded problem i of the batch; see _make_problem for the families.  r04 (wider template):
     obj_weights=True adds per-joint weights w_j in [0.4, 3] of the smoothing objective (``obj_w``; a QuadExpr built from a
     weighted difference matrix, prob.py:88-104, 348-367); per_step=True (program family) gives every timestep its own
     parameter vector (``row_params`` of shape (T, n_params): obstacles that drift and pulse along the horizon -- each
     timestep's Expr closes over its own data, expr.py:22-41).  Both draw from their own generators: every other number of
-    the problem is what it is without them.  lin_rows=True adds the general affine rows of ``general_rows`` (``lin_gen``)."""
+    the problem is what it is without them.  lin_rows=True adds the general affine rows of ``general_rows`` (``lin_gen``).
+    block_obj="effort" / "ee-path" / "smooth3": the block-objective workloads of make_block_obj_problem (their variant, dof and
+    horizon unless given)."""
+    if block_obj is not None:
+        return make_block_obj_problem(i, block_obj, obj_weights=obj_weights, per_step=per_step, lin_rows=lin_rows,
+                                      acc_weights=acc_weights, circles=circles, **kw)
     out = _make_problem(i, **kw)
     if circles:
         # r04: a SECOND kind of non-linear rows on every timestep: `circles` keep-out discs for the point (x[0], x[1]) IN FRONT of the

@@ -17,6 +17,9 @@ for name, kw in (("circles", {}), ("reach", dict(reach=True)), ("vel", dict(vel_
                  ("attract+steps+weights", dict(d=2, T=20, K=1, program=True, variant="attract", per_step=True, obj_weights=True)),
                  # shapes other than 7 x 20 on the patterns the wavefront tier takes (which tier is faster where)
                  ("point d=2 T=20", dict(d=2, T=20, K=1, O=3, point=True)), ("quad d=3 T=12", dict(d=3, T=12, K=1, O=4, quadratic=True)),
+                 # objective programs per constraint block (SCO_FAM_FLAG_OBJ_BLOCK) next to the same rows without the term
+                 ("dynamics 3x12", dict(d=3, T=12, K=1, program=True, variant="dynamics")), ("effort 3x12", dict(block_obj="effort")),
+                 ("sweep 7x20", dict(d=7, T=20, K=1, program=True, variant="sweep")), ("ee-path 7x20", dict(block_obj="ee-path")),
                  ("arm 4x24", dict(d=4, T=24, K=3, O=2)), ("arm 7x12", dict(T=12)), ("arm 5x16", dict(d=5, T=16, K=4, O=2)), ("arm 3x6", dict(d=3, T=6, K=2, O=2))):
     if ONLY and name not in ONLY.split(','):
         continue
@@ -25,6 +28,6 @@ for name, kw in (("circles", {}), ("reach", dict(reach=True)), ("vel", dict(vel_
     t = time.time(); res = sb.solve_batch(arrays); dt = time.time() - t
     tm = res.timing
     tier = "wavefront %d + other %d launches" % (tm.get("wv_launches", 0), tm.get("other_launches", 0))
-    print("%-24s [%s] wall %.2fs sco_it/s %.0f success %.3f admm iters/problem %.0f -> %.2f us per problem-iteration (admm %.0f ms, setup %.0f ms)" % (
+    print("%-24s [%s] wall %.2fs sco_it/s %.0f success %.3f admm iters/problem %.0f -> %.2f us per problem-iteration (admm %.0f ms, setup %.0f ms, convexify %.1f ms)" % (
         name, tier, dt, res.sqp_iters.sum() / dt, res.success.mean(), res.admm_iters.mean(),
-        1e3 * tm["admm_ms"] / (res.admm_iters.sum() / 256.0), tm["admm_ms"], tm["qp_setup_ms"]), flush=True)
+        1e3 * tm["admm_ms"] / (res.admm_iters.sum() / 256.0), tm["admm_ms"], tm["qp_setup_ms"], tm["convexify_ms"]), flush=True)
