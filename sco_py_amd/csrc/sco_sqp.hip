@@ -295,7 +295,9 @@ __device__ double min_eig_jacobi(const double *H, int d) {
         const double apq = A[p * d + q];
         if (fabs(apq) < 1e-300) continue;
         const double theta = (A[q * d + q] - A[p * d + p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        // |theta| beyond 1e150 would overflow theta^2: there sqrt(theta^2 + 1) = |theta| to the last bit
+        const double at = fabs(theta);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (at + (at > 1e150 ? at : sqrt(theta * theta + 1.0)));
         const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
         for (int k = 0; k < d; k++) {            // columns p, q
           const double rp = A[k * d + p], rq = A[k * d + q];

@@ -477,7 +477,10 @@ def block_obj_program(kind, d):
                of an arm with links of length 1 / dof (ee = sum_i l (cos, sin)(theta_0 + .. + theta_i));
     "smooth3"  span 3, dof >= 2, the "accel" rows, and a robust (pseudo-Huber) cost of the second difference a of the window,
                p[n] sqrt(1 + p[n + 1] |a|^2), plus a Gaussian well -p[n + 2] exp(-|x_t+1 - g|^2 / 0.08) on the middle point
-               around g = p[n + 3 : n + 5]."""
+               around g = p[n + 3 : n + 5];
+    "smooth4"  span 4, dof 2 .. 4, the "jerk" rows, and a robust (pseudo-Huber) cost of the third difference j of the window,
+               p[n] sqrt(1 + p[n + 1] |j|^2), plus a Gaussian well -p[n + 2] exp(-|x_t+2 - g|^2 / 0.08) on the third point
+               around g = p[n + 3 : n + 5] (a band of four blocks: every entry of P away from the ends sums four terms)."""
     key = ("block_obj", kind, d)
     if key in _PROGRAMS:
         return _PROGRAMS[key]
@@ -506,6 +509,12 @@ def block_obj_program(kind, d):
         ax, ay = X(0) - 2.0 * X(d) + X(2 * d), X(1) - 2.0 * X(d + 1) + X(2 * d + 1)
         term = P(n) * sqrt(1.0 + P(n + 1) * (ax ** 2 + ay ** 2)) - \
             P(n + 2) * exp(-((X(d) - P(n + 3)) ** 2 + (X(d + 1) - P(n + 4)) ** 2) / 0.08)
+    elif kind == "smooth4":
+        v, n = variant_rows("jerk", d), 8
+        jx = X(3 * d) - 3.0 * X(2 * d) + 3.0 * X(d) - X(0)
+        jy = X(3 * d + 1) - 3.0 * X(2 * d + 1) + 3.0 * X(d + 1) - X(1)
+        term = P(n) * sqrt(1.0 + P(n + 1) * (jx ** 2 + jy ** 2)) - \
+            P(n + 2) * exp(-((X(2 * d) - P(n + 3)) ** 2 + (X(2 * d + 1) - P(n + 4)) ** 2) / 0.08)
     else:
         raise ValueError("unknown block-objective workload %r" % (kind,))
     prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], block_objective=term, dof=d)
@@ -513,12 +522,13 @@ def block_obj_program(kind, d):
     return prog
 
 
-BLOCK_OBJ = {"effort": ("dynamics", 3, 12), "ee-path": ("sweep", 7, 20), "smooth3": ("accel", 2, 10)}
+BLOCK_OBJ = {"effort": ("dynamics", 3, 12), "ee-path": ("sweep", 7, 20), "smooth3": ("accel", 2, 10), "smooth4": ("jerk", 2, 10)}
 
 
 def make_block_obj_problem(i, kind, T=None, d=None, **kw):
     """Seeded problem i of a block-objective workload (block_obj_program): the problem of the underlying variant ("effort":
-    "dynamics" at dof 3, T = 12; "ee-path": "sweep" at dof 7, T = 20; "smooth3": "accel" at dof 2, T = 10) unchanged, plus the
+    "dynamics" at dof 3, T = 12; "ee-path": "sweep" at dof 7, T = 20; "smooth3": "accel" at dof 2, T = 10; "smooth4": "jerk" at
+    dof 2, T = 10) unchanged, plus the
     term's parameters from a generator of their own, appended to every parameter vector.  ``kw`` goes to make_problem
     (obj_weights, per_step, acc_weights, vel_limit, groups, ...)."""
     if kind not in BLOCK_OBJ:
@@ -537,6 +547,8 @@ def make_block_obj_problem(i, kind, T=None, d=None, **kw):
         g = (1 - a) * out["start"][:2] + a * out["goal"][:2] + 0.1 * rng.standard_normal(2)
         if kind == "effort":
             extra = np.array([rng.uniform(0.02, 0.1), rng.uniform(0.01, 0.05), rng.uniform(0.005, 0.02), g[0], g[1]])
+        elif kind == "smooth4":
+            extra = np.array([rng.uniform(0.05, 0.2), rng.uniform(2.0, 8.0), rng.uniform(0.005, 0.02), g[0], g[1]])
         else:
             extra = np.array([rng.uniform(0.05, 0.2), rng.uniform(5.0, 20.0), rng.uniform(0.005, 0.02), g[0], g[1]])
     par = np.asarray(out["row_params"], dtype=np.float64)
@@ -579,7 +591,7 @@ def make_problem(i, obj_weights=False, per_step=False, lin_rows=False, circles=0
     parameter vector (``row_params`` of shape (T, n_params): obstacles that drift and pulse along the horizon -- each
     timestep's Expr closes over its own data, expr.py:22-41).  Both draw from their own generators: every other number of
     the problem is what it is without them.  lin_rows=True adds the general affine rows of ``general_rows`` (``lin_gen``).
-    block_obj="effort" / "ee-path" / "smooth3": the block-objective workloads of make_block_obj_problem (their variant, dof and
+    block_obj="effort" / "ee-path" / "smooth3" / "smooth4": the block-objective workloads of make_block_obj_problem (their variant, dof and
     horizon unless given)."""
     if block_obj is not None:
         return make_block_obj_problem(i, block_obj, obj_weights=obj_weights, per_step=per_step, lin_rows=lin_rows,

@@ -22,7 +22,8 @@ from blockobj_cases import CASES as GOLDEN        # noqa: E402
 
 CASES = [("effort", dict(T=6)), ("effort", dict(T=6, per_step=True)), ("effort", dict(T=6, obj_weights=True, acc_weights=True)),
          ("effort", dict(T=6, vel_limit=0.6, groups="halves")), ("ee-path", dict(T=5)), ("effort", dict(T=8, analytic=True)),
-         ("smooth3", dict(T=8)), ("smooth3", dict(acc_weights=True)), ("smooth3", dict(d=3, T=9, per_step=True, obj_weights=True))]
+         ("smooth3", dict(T=8)), ("smooth3", dict(acc_weights=True)), ("smooth3", dict(d=3, T=9, per_step=True, obj_weights=True)),
+         ("smooth4", dict(T=8)), ("smooth4", dict(d=4, T=6, acc_weights=True))]       # span 4; 16-number blocks
 
 
 @pytest.mark.parametrize("case", range(len(GOLDEN)))
@@ -69,7 +70,7 @@ def test_batch_follows_the_flat_oracle(gpu, case):
     kind, kw = CASES[case]
     kw = dict(kw); analytic = kw.pop("analytic", False)
     arrays, probs = wl.make_batch(4, first=10 * case, block_obj=kind, **kw)
-    assert arrays["row_program"].span == (3 if kind == "smooth3" else 2)
+    assert arrays["row_program"].span == {"smooth3": 3, "smooth4": 4}.get(kind, 2)
     res = sb.solve_batch(arrays, analytic_jac=analytic)
     assert np.all(res.qp_solves > 1)
     for b in range(4):
