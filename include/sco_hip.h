@@ -273,6 +273,16 @@ void sco_sqp_default_params(sco_sqp_params *p);
                                   dense band of rows max(0, t - span + 1) * dof .. t * dof + j (plus (t - 2, j) with
                                   SCO_FAM_FLAG_ACC_COST and span 2), and overlapping blocks add up in block order */
 
+#define SCO_FAM_FLAG_OBJ_WIDE 1024    /* opt-in, OR-ed with exactly one of SCO_FAM_STATE_PROGRAM | SCO_FAM_FLAG_OBJ_BLOCK (span
+                                  2 .. 4, span * dof <= 32) and SCO_FAM_STATE_PROGRAM | SCO_FAM_FLAG_OBJ_PROGRAM (span 1, dof <= 32):
+                                  WIDE objective terms of up to 32 numbers.  The eigenvalue shift of a term runs on one wavefront
+                                  with the term's matrix in LDS -- the cyclic Jacobi sweep of the per-thread path, rotation for
+                                  rotation -- and the degree-2 model is built lane-parallel.  Terms of 16 numbers or fewer are
+                                  accepted as well and take the same path.  Refused with SCO_ERR_ARG alone, with
+                                  SCO_FAM_FLAG_EE_COST, with another family, with both objective flags and beyond 32 numbers;
+                                  SCO_ERR_CAPACITY (with a message) when the terms' Hessians, batch x terms x n^2 doubles, do not
+                                  fit in device memory */
+
 typedef struct sco_trajopt_desc {
   int batch;
   int dof;

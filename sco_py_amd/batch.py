@@ -26,6 +26,7 @@ SCO_FAM_FLAG_EE_COST = 64
 SCO_FAM_FLAG_OBJ_PROGRAM = 128
 SCO_FAM_FLAG_ACC_COST = 256
 SCO_FAM_FLAG_OBJ_BLOCK = 512
+SCO_FAM_FLAG_OBJ_WIDE = 1024
 TRACE_W = 8
 
 
@@ -98,6 +99,7 @@ class TrajOptBatch(object):
                              "block's rows are equalities; leave n_eq_rows out)" % (int(n_eq_rows), prog.n_eq))
         self.obj_program = bool(prog is not None and prog.objective)
         self.obj_block = bool(prog is not None and prog.block_objective)     # an objective term per block (span 2 .. 4)
+        self.obj_wide = bool(prog is not None and prog.wide)     # the term on the wide path (up to 32 numbers, SCO_FAM_FLAG_OBJ_WIDE)
         self.n_blocks = self.T - self.span + 1
         desc = _lib.TrajoptDesc(self.B, self.d, self.T, self.K, self.O,
                                 (SCO_FAM_STATE_PROGRAM if self.program else SCO_FAM_STATE_QUADRATIC if self.quadratic else
@@ -108,6 +110,7 @@ class TrajOptBatch(object):
                                 (SCO_FAM_FLAG_EE_COST if self.ee_cost else 0) |
                                 (SCO_FAM_FLAG_OBJ_PROGRAM if self.obj_program else 0) |
                                 (SCO_FAM_FLAG_OBJ_BLOCK if self.obj_block else 0) |
+                                (SCO_FAM_FLAG_OBJ_WIDE if self.obj_wide else 0) |
                                 (SCO_FAM_FLAG_ACC_COST if bool(acc_cost) else 0),
                                 1 if analytic_jac else 0, int(prox_count), self.span, self.n_eq)
         self.acc_cost = bool(acc_cost)
@@ -176,7 +179,7 @@ class TrajOptBatch(object):
                 raise ValueError("the program family needs row_program (sco_py_amd.rowexpr.compile_rows) and row_params (B, n_params)")
             if row_program.n_rows != O - self.circle_rows or row_program.n_state > d * self.span or row_program.span != self.span or \
                     row_program.n_eq != self.n_eq or row_program.objective != self.obj_program or \
-                    row_program.block_objective != self.obj_block:
+                    row_program.block_objective != self.obj_block or row_program.wide != self.obj_wide:
                 raise ValueError("the program has %d rows (%d equalities) over %d state coordinates, span %d, objective term %s; the "
                                  "batch was created for %d rows per block (%d equalities), dof %d, span %d, objective term %s"
                                  % (row_program.n_rows, row_program.n_eq, row_program.n_state, row_program.span, row_program.objective,

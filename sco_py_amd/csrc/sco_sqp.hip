@@ -636,11 +636,78 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_post_kernel(SqpDev s, QpDe
   }
 }
 
+// SCO_FAM_FLAG_OBJ_WIDE: eigenvalue shift and degree-2 model of the objective terms (n <= 32 numbers each), ONE WAVEFRONT per
+// term.  The term's matrix sits in dynamic LDS with row stride WIDE_LD = 33 doubles, so lane k's column entry (k, p) and a row
+// (p, 0 .. n-1) are both free of bank conflicts.  The cyclic Jacobi sweep is min_eig_jacobi's, rotation for rotation (12
+// sweeps, the 1e-300 skip, the 1e150 guard): every lane reads the rotation's scalars from LDS and computes c, s itself; lanes
+// k < n rotate the column pair (k, p), (k, q), then -- after a wavefront-scope fence -- the row pair (p, k), (q, k).  Every
+// element sees the same operations in the same order as in the per-thread sweep.  The model: lane j forms (x'H)_j and
+// A_j = g_j - (x'H)_j; lane 0 sums x'Hx and g.x in j order, as the per-thread path does.  No workgroup barrier inside.
+#define WIDE_LD 33
+#define WIDE_WAVE_LDS (SCO_STATE_MAX * WIDE_LD + 2 * SCO_STATE_MAX)     // doubles per wavefront: the matrix, x'H, g
+#define WIDE_LDS_BYTES (NWAVE * WIDE_WAVE_LDS * sizeof(double))
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ void obj_shift_model_wide(double *oH, double *oA, double *ob, const double *of0, const double *x, int d, int n,
+                                     int NO, int tid) {
+  extern __shared__ double wide_lds[];
+  const int lane = tid & 63, wave = tid >> 6;
+  double *A = wide_lds + wave * WIDE_WAVE_LDS, *xh = A + SCO_STATE_MAX * WIDE_LD, *gl = xh + SCO_STATE_MAX;
+  for (int t = wave; t < NO; t += NWAVE) {
+    double *Ht = oH + (size_t)t * n * n;
+    const double *th = x + t * d;
+    for (int e = lane; e < n * n; e += 64) A[(e / n) * WIDE_LD + e % n] = Ht[e];
+    wave_lds_sync();
+    for (int sweep = 0; sweep < 12; sweep++)
+      for (int p = 0; p < n - 1; p++)
+        for (int q = p + 1; q < n; q++) {
+          const double apq = A[p * WIDE_LD + q];
+          if (fabs(apq) < 1e-300) continue;
+          const double theta = (A[q * WIDE_LD + q] - A[p * WIDE_LD + p]) / (2.0 * apq);
+          const double at = fabs(theta);
+          const double tr = (theta >= 0.0 ? 1.0 : -1.0) / (at + (at > 1e150 ? at : sqrt(theta * theta + 1.0)));
+          const double c = 1.0 / sqrt(tr * tr + 1.0), sn = tr * c;
+          if (lane < n) {                                   // columns p, q
+            const double rp = A[lane * WIDE_LD + p], rq = A[lane * WIDE_LD + q];
+            A[lane * WIDE_LD + p] = c * rp - sn * rq; A[lane * WIDE_LD + q] = sn * rp + c * rq;
+          }
+          wave_lds_sync();
+          if (lane < n) {                                   // rows p, q
+            const double rp = A[p * WIDE_LD + lane], rq = A[q * WIDE_LD + lane];
+            A[p * WIDE_LD + lane] = c * rp - sn * rq; A[q * WIDE_LD + lane] = sn * rp + c * rq;
+          }
+          wave_lds_sync();
+        }
+    double lam = A[0];
+    for (int i = 1; i < n; i++) lam = fmin(lam, A[i * WIDE_LD + i]);
+    if (lane < n) {
+      if (lam < 0.0) Ht[lane * n + lane] -= lam;           // (lane j touches only its own diagonal entry)
+      const double g = oA[t * n + lane];
+      double acc = 0.0;
+      for (int i = 0; i < n; i++) acc += th[i] * Ht[i * n + lane];
+      xh[lane] = acc; gl[lane] = g;
+      oA[t * n + lane] = g - acc;
+    }
+    wave_lds_sync();
+    if (lane == 0) {
+      double xHx = 0.0, gx = 0.0;
+      for (int j = 0; j < n; j++) { xHx += xh[j] * th[j]; gx += gl[j] * th[j]; }
+      ob[t] = (0.5 * xHx - gx) + of0[t];
+    }
+    wave_lds_sync();                                        // the next term overwrites A, x'H and g
+  }
+}
+
 // --------------------------------------------------------------------------
 // sqp_pre: convexify + update_obj + merit + save (for problems that start a new
-// SQP iteration), then the trust-region bounds (for every active problem)
+// SQP iteration), then the trust-region bounds (for every active problem).
+// WIDE (SCO_FAM_FLAG_OBJ_WIDE, sqp_pre_wide_kernel): the objective terms' shift and model by obj_shift_model_wide
 // --------------------------------------------------------------------------
-__global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, SqpParamsDev p) {
+template <bool WIDE>
+__device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev &p) {
   const int g = blockIdx.x + s.b0, tid = threadIdx.x;
   const int b = s.list ? s.list[g] : g;        // round selection: only the listed problems are visited
   if (b < 0) return;
@@ -824,6 +891,8 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
       }
       __syncthreads();
       // eigenvalue shift, then Q = H, A = g - x'H, b = 1/2 x'Hx - g.x + f (expr.py:145-152)
+      if constexpr (WIDE) obj_shift_model_wide(oH, oA, ob, of0, x, d, dO, NO, tid);
+      else
       for (int t = tid; t < NO; t += SCO_BLOCK) {
         double *Ht = oH + (size_t)t * dO * dO;
         const double *th = x + t * d;
@@ -932,6 +1001,9 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, 
     for (int i = tid; i < n_x; i += SCO_BLOCK) { l[base + i] = xs[i] - trust; u[base + i] = xs[i] + trust; }
   }
 }
+__global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_kernel(SqpDev s, QpDev q1, SqpParamsDev p) { sqp_pre_body<false>(s, q1, p); }
+// launched with WIDE_LDS_BYTES of dynamic LDS
+__global__ __launch_bounds__(SCO_BLOCK) void sqp_pre_wide_kernel(SqpDev s, QpDev q1, SqpParamsDev p) { sqp_pre_body<true>(s, q1, p); }
 
 // --------------------------------------------------------------------------
 // sqp_post: model merit, new merit, decision
@@ -1189,8 +1261,11 @@ extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int
   }
   const int fam = desc->family & 15, span = desc->span > 0 ? desc->span : 1;
   const bool statefam = fam == SCO_FAM_STATE_QUADRATIC || fam == SCO_FAM_STATE_PROGRAM;
+  // widest objective term: the per-thread eigenvalue sweep's, or with SCO_FAM_FLAG_OBJ_WIDE the wavefront's
+  const bool objwide = (desc->family & SCO_FAM_FLAG_OBJ_WIDE) != 0;
+  const int objmax = objwide ? SCO_STATE_MAX : OBJ_DMAX;
   if (desc->batch <= 0 || desc->dof <= 0 || desc->horizon < 2 || desc->n_points <= 0 || desc->n_obstacles <= 0 ||
-      desc->horizon > 256 || (desc->family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_ACC_COST | SCO_FAM_FLAG_OBJ_BLOCK)) ||
+      desc->horizon > 256 || (desc->family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_ACC_COST | SCO_FAM_FLAG_OBJ_BLOCK | SCO_FAM_FLAG_OBJ_WIDE)) ||
       ((desc->family & SCO_FAM_FLAG_EE_COST) && desc->dof > OBJ_DMAX) || ((desc->family & SCO_FAM_FLAG_ACC_COST) && desc->horizon < 3) ||
       (fam != SCO_FAM_ARM_CIRCLES && fam != SCO_FAM_ARM_REACH && fam != SCO_FAM_POINT_CIRCLES && !statefam) ||
       (fam == SCO_FAM_POINT_CIRCLES && (desc->n_points != 1 || desc->dof < 2 || (desc->family & SCO_FAM_FLAG_EE_COST))) ||
@@ -1200,10 +1275,13 @@ extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int
       desc->span < 0 || desc->span > 4 || desc->n_eq_rows < 0 || desc->n_eq_rows > desc->n_obstacles ||
       (span > 1 && fam != SCO_FAM_STATE_PROGRAM) || (desc->n_eq_rows > 0 && !statefam) ||
       (fam == SCO_FAM_STATE_PROGRAM && (span * desc->dof > SCO_STATE_MAX || span >= desc->horizon)) ||
-      ((desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) && (fam != SCO_FAM_STATE_PROGRAM || span != 1 || desc->dof > OBJ_DMAX)) ||
+      ((desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) && (fam != SCO_FAM_STATE_PROGRAM || span != 1 || desc->dof > objmax)) ||
       // an objective program per constraint block: span 2 .. 4, the block's state fits the per-thread eigenvalue sweep
-      ((desc->family & SCO_FAM_FLAG_OBJ_BLOCK) && (fam != SCO_FAM_STATE_PROGRAM || span < 2 || span * desc->dof > OBJ_DMAX ||
-                                                   (desc->family & (SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_EE_COST))))) {
+      ((desc->family & SCO_FAM_FLAG_OBJ_BLOCK) && (fam != SCO_FAM_STATE_PROGRAM || span < 2 || span * desc->dof > objmax ||
+                                                   (desc->family & (SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_EE_COST)))) ||
+      // SCO_FAM_FLAG_OBJ_WIDE: opt-in, the program family with exactly one of its two objective flags
+      (objwide && (fam != SCO_FAM_STATE_PROGRAM || (desc->family & SCO_FAM_FLAG_EE_COST) ||
+                   !(desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) == !(desc->family & SCO_FAM_FLAG_OBJ_BLOCK)))) {
     sco_set_error("sco_sqp_create: bad descriptor"); return SCO_ERR_ARG;
   }
   int ndev = 0;
@@ -1384,7 +1462,23 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
   AL(cw, (size_t)B) AL(ctgt, (size_t)B * 2)
   {
     const size_t NO = oblk ? NBt : T, dO = oblk ? ds : d;     // objective terms and their state
-    AL(oH, cost ? (size_t)B * NO * dO * dO : 1) AL(oA, cost ? (size_t)B * NO * dO : 1) AL(ob, cost ? (size_t)B * NO : 1)
+    if (desc->family & SCO_FAM_FLAG_OBJ_WIDE) {
+      // a wide term's Hessians: B * NO * dO^2 doubles (2.1 GB at B = 1024, T = 256, dO = 32), refused when they do not fit
+      void *p = nullptr;
+      const size_t bytes = (size_t)B * NO * dO * dO * sizeof(double);
+      if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        char buf[200];
+        snprintf(buf, sizeof buf, "sco_sqp_create: the objective terms' Hessians (batch x terms x n^2 doubles) need %zu bytes of "
+                 "device memory; use a smaller batch", bytes);
+        sco_set_error(buf); return SCO_ERR_CAPACITY;
+      }
+      h->allocs.push_back(p); s.oH = (double *)p;
+      SCO_HIP(hipMemset(p, 0, bytes));
+    } else {
+      AL(oH, cost ? (size_t)B * NO * dO * dO : 1)
+    }
+    AL(oA, cost ? (size_t)B * NO * dO : 1) AL(ob, cost ? (size_t)B * NO : 1)
   }
 #undef AL
   { int *p; if ((rc = sq_alloc(h, (size_t)n_x, &p))) return rc; s.ppos = p;
@@ -1994,7 +2088,10 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
       SCO_HIP(hipGetLastError());
       sg.list = s.list_buf;
     }
-    hipLaunchKernelGGL(sqp_pre_kernel, dim3(nwg), block, 0, r.st, sg, h->qp1->d, p);
+    if (h->desc.family & SCO_FAM_FLAG_OBJ_WIDE)   // the objective terms' sweep on one wavefront per term, matrices in LDS
+      hipLaunchKernelGGL(sqp_pre_wide_kernel, dim3(nwg), block, WIDE_LDS_BYTES, r.st, sg, h->qp1->d, p);
+    else
+      hipLaunchKernelGGL(sqp_pre_kernel, dim3(nwg), block, 0, r.st, sg, h->qp1->d, p);
     SCO_HIP(hipGetLastError());
     gmark(g, 0);
     hipEvent_t gm = gevent(g); r.stage.push_back(1);

@@ -25,6 +25,7 @@ import numpy as np
 OP_END, OP_X, OP_P, OP_C, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_SIN, OP_COS, OP_SQRT, OP_EXP, OP_SQUARE = range(14)
 STACK = 16
 OBJ_DMAX = 16          # widest state of an objective term (the device's per-thread eigenvalue sweep)
+OBJ_WIDE_DMAX = 32     # ... of a wide one (SCO_FAM_FLAG_OBJ_WIDE: the wavefront-cooperative sweep in LDS)
 
 
 class Node(object):
@@ -74,13 +75,15 @@ def exp(a): return Node(OP_EXP, kids=(Node.lift(a),))
 class Program(object):
     """Rows compiled to the wire format of sco_sqp_load_program."""
 
-    def __init__(self, words, row_ptr, consts, n_eq=0, span=1, objective=False, block_objective=False):
+    def __init__(self, words, row_ptr, consts, n_eq=0, span=1, objective=False, block_objective=False, wide=False):
         self.words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1, 2)
         self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
         self.consts = np.ascontiguousarray(consts, dtype=np.float64)
         self.objective = bool(objective)           # the LAST program is an objective term of a timestep, not a constraint row
         self.block_objective = bool(block_objective)   # ... or an objective term of a whole block (span 2 .. 4)
+        self.wide = bool(wide)                     # the term takes the wide path (SCO_FAM_FLAG_OBJ_WIDE, up to 32 numbers)
         assert not (self.objective and self.block_objective)
+        assert not self.wide or self.objective or self.block_objective
         self.n_rows = len(self.row_ptr) - 1 - (1 if self.objective or self.block_objective else 0)      # constraint rows of a block
         self.n_eq = int(n_eq)                      # how many of them (the last ones) are equalities
         self.span = int(span)                      # timesteps per constraint block
@@ -175,16 +178,19 @@ class Program(object):
         return lambda x: float(self.evaluate(x, p, rows=[self.n_rows])[0])
 
 
-def compile_rows(rows, eq_rows=(), objective=None, span=1, block_objective=None, dof=None):
+def compile_rows(rows, eq_rows=(), objective=None, span=1, block_objective=None, dof=None, wide=False):
     """List of Node expressions -> Program.  ``rows``: inequality rows g_r(x, p) <= 0; ``eq_rows``: equality rows
     g_r(x, p) = 0 (they follow the inequalities in a block); ``objective``: a non-quadratic objective term f(x, p) of ONE
     timestep (span 1 only); ``block_objective``: a non-quadratic objective term f(x, p) of a whole BLOCK, x = its span * dof
     numbers (span 2 .. 4; SCO_FAM_FLAG_OBJ_BLOCK: span * dof <= 16 -- pass ``dof`` to have that checked here, otherwise the
-    term's highest X index is); ``span``: timesteps per constraint block (X(i) addresses i < span * dof)."""
+    term's highest X index is); ``span``: timesteps per constraint block (X(i) addresses i < span * dof); ``wide=True``:
+    the objective term (either kind) takes the wide path (SCO_FAM_FLAG_OBJ_WIDE) on up to 32 numbers (``Program.wide``)."""
     if span not in (1, 2, 3, 4) or (objective is not None and span != 1):
         raise ValueError("span is 1 .. 4; an objective term needs span 1")
     if block_objective is not None and (objective is not None or span == 1):
         raise ValueError("a block objective term needs span 2 .. 4 and excludes objective=")
+    if wide and objective is None and block_objective is None:
+        raise ValueError("wide=True needs an objective term (objective= or block_objective=)")
     term = objective if objective is not None else block_objective
     rows, eq_rows = list(rows), list(eq_rows)          # (generators are welcome: they are walked once, here)
     words, row_ptr, consts = [], [0], []
@@ -193,11 +199,16 @@ def compile_rows(rows, eq_rows=(), objective=None, span=1, block_objective=None,
         words.append((OP_END, 0))
         row_ptr.append(len(words))
     prog = Program(words, row_ptr, consts, n_eq=len(eq_rows), span=span, objective=objective is not None,
-                   block_objective=block_objective is not None)
+                   block_objective=block_objective is not None, wide=wide)
     if prog.block_objective:
         ds = span * int(dof) if dof is not None else prog.n_state
-        if ds > OBJ_DMAX:
-            raise ValueError("a block objective term works on span * dof <= %d numbers (got %d)" % (OBJ_DMAX, ds))
+        if ds > (OBJ_WIDE_DMAX if wide else OBJ_DMAX):
+            raise ValueError("a block objective term works on span * dof <= %d numbers (got %d)"
+                             % (OBJ_WIDE_DMAX if wide else OBJ_DMAX, ds))
+    if prog.objective and wide:
+        dw = int(dof) if dof is not None else prog.n_state
+        if dw > OBJ_WIDE_DMAX:
+            raise ValueError("a wide objective term works on dof <= %d numbers (got %d)" % (OBJ_WIDE_DMAX, dw))
     for r in range(len(prog.row_ptr) - 1):            # the same checks the C side makes, with Python errors
         sp = 0
         for op, arg in prog.words[prog.row_ptr[r]:prog.row_ptr[r + 1] - 1]:

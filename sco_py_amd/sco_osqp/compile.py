@@ -292,8 +292,11 @@ def _compile(prob):
     if nq and fam == "program" and pr["row_program"].block_objective:
         # SCO_FAM_FLAG_OBJ_BLOCK: one ProgramBlockObjExpr per constraint block, on that block's own Variable, with the rows'
         # program and the block's parameters
-        if span * d > rx.OBJ_DMAX:
+        wide = pr["row_program"].wide
+        if not wide and span * d > rx.OBJ_DMAX:
             _no("block objective terms on more than %d numbers (span * dof)" % rx.OBJ_DMAX)
+        if wide and span * d > rx.OBJ_WIDE_DMAX:
+            _no("wide block objective terms on more than %d numbers (span * dof)" % rx.OBJ_WIDE_DMAX)
         if len(nq) != n_blocks:
             _no("block objective terms: one per constraint block")
         rp = pr["row_params"]
@@ -304,7 +307,7 @@ def _compile(prob):
                 _no("a block objective term is not on its constraint block's Variable")
             if be.expr.program is not pr["row_program"] or not _same(be.expr.params, rp[t] if np.ndim(rp) == 2 else rp):
                 _no("a block objective term has another program than the rows, or other parameters than its block's")
-        key_fam = key_fam + ("block_obj",)
+        key_fam = key_fam + ("block_obj",) + (("wide",) if wide else ())
     elif nq:
         if len(nq) != T:
             _no("objective terms: one per timestep")
@@ -320,6 +323,10 @@ def _compile(prob):
                 _no("per-timestep objective parameters")
             pr["cost_weight"] = o0.weight; pr["cost_target"] = o0.target.copy()
         elif o0.kind == "program_obj" and fam == "program" and span == 1:
+            if pr["row_program"].wide and d > rx.OBJ_WIDE_DMAX:
+                _no("wide objective terms on more than %d numbers (dof)" % rx.OBJ_WIDE_DMAX)
+            if pr["row_program"].wide:
+                key_fam = key_fam + ("wide",)
             rp = pr["row_params"]
             if any(be.expr.program is not pr["row_program"] or not _same(be.expr.params, rp[t] if np.ndim(rp) == 2 else rp)
                    for t, be in enumerate(nq)):

@@ -268,7 +268,7 @@ def corridor_program(d):
     return _PROGRAMS[d]
 
 
-def variant_program(variant, d):
+def variant_program(variant, d, wide=False):
     """Programs of the r03 variants of the program family (compiled once per (variant, dof)):
 
     "sweep"     span 2, dof >= 2: the MIDPOINT of the step (x_t, x_t+1) keeps out of two discs whose radius grows with the
@@ -285,12 +285,13 @@ def variant_program(variant, d):
                 acceleration limit that tightens with height -- and two keep-out discs on the MIDDLE timestep;
     "jerk"      (r04) span 4, dof >= 2: the squared third difference |x_t+3 - 3 x_t+2 + 3 x_t+1 - x_t|^2 <= p[6]^2, a keep-out disc
                 on the centroid of the four points whose radius grows with the squared chord |x_t+3 - x_t|^2, one on x_t+1."""
-    key = (variant, d)
+    key = (variant, d) + (("wide",) if wide else ())      # wide=True: the objective term on the wide path ("attract")
     if key in _PROGRAMS:
         return _PROGRAMS[key]
     from .rowexpr import compile_rows
     v = variant_rows(variant, d)
-    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], objective=v["objective"])
+    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], objective=v["objective"], wide=wide,
+                        **(dict(dof=d) if wide else {}))
     if variant == "attract":
         assert prog.n_rows == corridor_program(d).n_rows
     _PROGRAMS[key] = prog
@@ -464,7 +465,7 @@ def make_program_variant(i, variant, d=2, T=12, noise=0.03, groups=None, vel_lim
     return out
 
 
-def block_obj_program(kind, d):
+def block_obj_program(kind, d, wide=False):
     """Programs of the block-objective workloads (SCO_FAM_FLAG_OBJ_BLOCK): the rows of a variant plus ONE non-quadratic
     objective term per block, compiled once per (kind, dof).  The term's parameters follow the rows' (n = the variant's
     parameter count):
@@ -480,8 +481,9 @@ def block_obj_program(kind, d):
                around g = p[n + 3 : n + 5];
     "smooth4"  span 4, dof 2 .. 4, the "jerk" rows, and a robust (pseudo-Huber) cost of the third difference j of the window,
                p[n] sqrt(1 + p[n + 1] |j|^2), plus a Gaussian well -p[n + 2] exp(-|x_t+2 - g|^2 / 0.08) on the third point
-               around g = p[n + 3 : n + 5] (a band of four blocks: every entry of P away from the ends sums four terms)."""
-    key = ("block_obj", kind, d)
+               around g = p[n + 3 : n + 5] (a band of four blocks: every entry of P away from the ends sums four terms).
+    wide=True (SCO_FAM_FLAG_OBJ_WIDE) allows span * dof <= 32: ee-path dof <= 16, smooth3 dof <= 10, smooth4 dof <= 8."""
+    key = ("block_obj", kind, d) + (("wide",) if wide else ())
     if key in _PROGRAMS:
         return _PROGRAMS[key]
     from .rowexpr import X, P, sin, cos, sqrt, exp, compile_rows
@@ -517,7 +519,7 @@ def block_obj_program(kind, d):
             P(n + 2) * exp(-((X(2 * d) - P(n + 3)) ** 2 + (X(2 * d + 1) - P(n + 4)) ** 2) / 0.08)
     else:
         raise ValueError("unknown block-objective workload %r" % (kind,))
-    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], block_objective=term, dof=d)
+    prog = compile_rows(v["rows"], eq_rows=v["eq_rows"], span=v["span"], block_objective=term, dof=d, wide=wide)
     _PROGRAMS[key] = prog
     return prog
 
@@ -525,12 +527,17 @@ def block_obj_program(kind, d):
 BLOCK_OBJ = {"effort": ("dynamics", 3, 12), "ee-path": ("sweep", 7, 20), "smooth3": ("accel", 2, 10), "smooth4": ("jerk", 2, 10)}
 
 
-def make_block_obj_problem(i, kind, T=None, d=None, **kw):
+def make_block_obj_problem(i, kind, T=None, d=None, wide=False, **kw):
     """Seeded problem i of a block-objective workload (block_obj_program): the problem of the underlying variant ("effort":
     "dynamics" at dof 3, T = 12; "ee-path": "sweep" at dof 7, T = 20; "smooth3": "accel" at dof 2, T = 10; "smooth4": "jerk" at
     dof 2, T = 10) unchanged, plus the
     term's parameters from a generator of their own, appended to every parameter vector.  ``kw`` goes to make_problem
-    (obj_weights, per_step, acc_weights, vel_limit, groups, ...)."""
+    (obj_weights, per_step, acc_weights, vel_limit, groups, ...).  wide=True: the term on the wide path (block_obj_program);
+    kind "attract" is the span-1 objective term of a timestep (the "attract" variant, dof 20, T = 12 unless given) on it."""
+    if kind == "attract":
+        out = make_problem(i, program=True, variant="attract", d=20 if d is None else int(d), T=12 if T is None else int(T), **kw)
+        out["row_program"] = variant_program("attract", out["d"], wide=wide)
+        return out
     if kind not in BLOCK_OBJ:
         raise ValueError("unknown block-objective workload %r" % (kind,))
     if kw.get("circles"):
@@ -556,7 +563,7 @@ def make_block_obj_problem(i, kind, T=None, d=None, **kw):
         out["row_params"] = np.concatenate([par, np.broadcast_to(extra, (par.shape[0], extra.shape[0]))], axis=1)
     else:
         out["row_params"] = np.concatenate([par, extra])
-    out["row_program"] = block_obj_program(kind, d)
+    out["row_program"] = block_obj_program(kind, d, wide=wide)
     return out
 
 

@@ -20,6 +20,10 @@ for name, kw in (("circles", {}), ("reach", dict(reach=True)), ("vel", dict(vel_
                  # objective programs per constraint block (SCO_FAM_FLAG_OBJ_BLOCK) next to the same rows without the term
                  ("dynamics 3x12", dict(d=3, T=12, K=1, program=True, variant="dynamics")), ("effort 3x12", dict(block_obj="effort")),
                  ("sweep 7x20", dict(d=7, T=20, K=1, program=True, variant="sweep")), ("ee-path 7x20", dict(block_obj="ee-path")),
+                 # wide objective terms (SCO_FAM_FLAG_OBJ_WIDE): the same ee-path on the wide path, then terms of 24 to 32 numbers
+                 ("ee-path 7x20 wide", dict(block_obj="ee-path", wide=True)), ("ee-path 12x20 wide", dict(block_obj="ee-path", d=12, wide=True)),
+                 ("ee-path 16x12 wide", dict(block_obj="ee-path", d=16, T=12, wide=True)), ("smooth3 8x12 wide", dict(block_obj="smooth3", d=8, T=12, wide=True)),
+                 ("smooth4 8x12 wide", dict(block_obj="smooth4", d=8, T=12, wide=True)), ("attract 20x12 wide", dict(block_obj="attract", wide=True)),
                  ("arm 4x24", dict(d=4, T=24, K=3, O=2)), ("arm 7x12", dict(T=12)), ("arm 5x16", dict(d=5, T=16, K=4, O=2)), ("arm 3x6", dict(d=3, T=6, K=2, O=2))):
     if ONLY and name not in ONLY.split(','):
         continue
