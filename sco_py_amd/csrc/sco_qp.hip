@@ -1311,6 +1311,12 @@ extern "C" int sco_debug_qp_tiers(const sco_qp *qp) {
   return (qp->use_rl ? 1 : 0) | (qp->use_reg ? 2 : 0) | (qp->use_fast ? 4 : 0) | (qp->use_big ? 8 : 0) | (qp->use_bt ? 16 : 0) | (qp->use_wv ? 32 : 0) |
          ((qp->use_bt && qp->bt.use_mfma) ? 64 : 0);
 }
+// Iterations run by the wavefront kernel on this handle since the counter was last reset (only the SQP layer resets it): a
+// test reads it before and after a solve to see which problems that kernel really took.  0 on a handle without the tier.
+extern "C" int sco_debug_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
+  if (!qp || !out) return SCO_ERR_ARG;
+  return sco_qp_wv_iters(qp, out);
+}
 extern "C" int sco_debug_plan_get(const char *name, int *out, int cap) {
   const QpPlan &p = g_dbg_plan;
   const std::vector<int> *v = nullptr;

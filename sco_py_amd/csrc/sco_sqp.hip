@@ -2096,10 +2096,13 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
     gmark(g, 0);
     hipEvent_t gm = gevent(g); r.stage.push_back(1);
     const QpGroup win{r.b0, nwg, r.st, sg.list, has_wv ? (wv_round ? 2 : 1) : 0};
-    if (wv_round) wv_rounds++;
+    // without round selection (at most one problem per CU) the launch itself goes by its size (sco_qp_launch_sliced): with
+    // SCO_WV_MIN_PER_CU lowered such a round runs on the wavefront tier too, and is counted as one
+    const bool wv_plain = !has_wv && sco_qp_has_wv(h->qp1, &qsl) && nwg >= wv_min;
+    if (wv_round || wv_plain) wv_rounds++;
     const int rc_ = sco_qp_launch_sliced(h->qp1, &qsl, s.newqp, s.active, slice_req, gm, nullptr, (G > 1 || select) ? &win : nullptr);
     if (rc_) return rc_;
-    gmark(g, wv_round ? 5 : 2);
+    gmark(g, (wv_round || wv_plain) ? 5 : 2);
     hipLaunchKernelGGL(sqp_post_kernel, dim3(nwg), block, 0, r.st, sg, h->qp1->d, p);
     SCO_HIP(hipGetLastError());
     gmark(g, 3);
