@@ -58,8 +58,6 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #endif
 #if WV_VARIANT == 1
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
-#else
-#define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #k " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(g))
 #endif
 
 __host__ __device__ __forceinline__ size_t wv_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }   // packed lower, j <= i
@@ -256,7 +254,7 @@ struct WvArgs {
   const int *Ap, *Ai, *Rp, *Rj, *Rpos, *Fp, *Fi, *Fpos;
   double *x, *y, *resid; int *status, *iters, *prog;
   double *sx, *sz, *sy, *st, *sg;
-  int ablate;        // diagnostic (SCO_WV_ABLATE): 1 = no sweeps, 2 = no row passes, 16 = no termination test behind the checked iteration, 64 = no infeasibility certificates (timing only, results wrong)
+  int ablate;        // diagnostic (SCO_WV_ABLATE, read by builds with -DWV_ABLATE only): 1 = no sweeps, 2 = no row passes, 16 = no termination test behind the checked iteration, 64 = no infeasibility certificates (timing only, results wrong)
 };
 
 // Wavefront-wide max / sum in registers: two DPP quad steps, two DPP mirror steps inside a 16-lane row, then the row and
@@ -425,20 +423,30 @@ template <int BS>
 __device__ __forceinline__ double wv_matvec(double acc, double w, const WvRow<BS> &g) {
   const d2 g0 = g.a, g1 = g.b, g2 = g.c, g3 = g.d;
   // two accumulators: a dependent v_fmac_f64_dpp issues every 8.5 cycles, two interleaved chains every 6.5
-  // (scripts/microbench/wave_cost.hip).  The FIRST instruction of both chains sits in one asm statement behind the wait
-  // states: the two chains are independent, so as separate statements the scheduler was free to put the second chain's
-  // first broadcast directly behind the instruction that writes w (seen as wrong results of one build, r04).
+  // (scripts/microbench/wave_cost.hip).  The WHOLE chain sits in one asm statement behind the wait states its first
+  // broadcast needs: as separate statements the scheduler was free to put a VALU write of w directly in front of a later
+  // broadcast (seen as wrong results of one build, r04, when only the first pair was tied together), and the hazard
+  // recogniser does not look into inline assembly.
   double acc2 = 0.0;
 #if WV_VARIANT == 1
   WV_FMAC_DPP(acc, w, g0.x, 0); WV_FMAC_DPP(acc2, w, g0.y, 1);
-#else
-  asm("s_nop 1\n\tv_fmac_f64_dpp %0, %2, %3 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %1, %2, %4 row_newbcast:1 row_mask:0xf bank_mask:0xf"
-      : "+v"(acc), "+v"(acc2) : "v"(w), "v"(g0.x), "v"(g0.y));
-#endif
   WV_FMAC_DPP(acc, w, g1.x, 2); WV_FMAC_DPP(acc2, w, g1.y, 3);
   WV_FMAC_DPP(acc, w, g2.x, 4); WV_FMAC_DPP(acc2, w, g2.y, 5); WV_FMAC_DPP(acc, w, g3.x, 6);
   if (BS > 7) WV_FMAC_DPP(acc2, w, g3.y, 7);
+#else
+#define WV_DPP_STEP(acc, g, k) "v_fmac_f64_dpp " acc ", %2, " g " row_newbcast:" #k " row_mask:0xf bank_mask:0xf\n\t"
+  if (BS > 7)
+    asm("s_nop 1\n\t"
+        WV_DPP_STEP("%0", "%3", 0) WV_DPP_STEP("%1", "%4", 1) WV_DPP_STEP("%0", "%5", 2) WV_DPP_STEP("%1", "%6", 3)
+        WV_DPP_STEP("%0", "%7", 4) WV_DPP_STEP("%1", "%8", 5) WV_DPP_STEP("%0", "%9", 6) WV_DPP_STEP("%1", "%10", 7)
+        : "+v"(acc), "+v"(acc2) : "v"(w), "v"(g0.x), "v"(g0.y), "v"(g1.x), "v"(g1.y), "v"(g2.x), "v"(g2.y), "v"(g3.x), "v"(g3.y));
+  else
+    asm("s_nop 1\n\t"
+        WV_DPP_STEP("%0", "%3", 0) WV_DPP_STEP("%1", "%4", 1) WV_DPP_STEP("%0", "%5", 2) WV_DPP_STEP("%1", "%6", 3)
+        WV_DPP_STEP("%0", "%7", 4) WV_DPP_STEP("%1", "%8", 5) WV_DPP_STEP("%0", "%9", 6)
+        : "+v"(acc), "+v"(acc2) : "v"(w), "v"(g0.x), "v"(g0.y), "v"(g1.x), "v"(g1.y), "v"(g2.x), "v"(g2.y), "v"(g3.x));
+#undef WV_DPP_STEP
+#endif
   return acc + acc2;
 }
 
@@ -459,6 +467,13 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
   if (b < 0 || (a.active && !a.active[b])) return;
   if (!a.ok[b]) return;                          // not a penalty-QP value structure: the row-local kernel solves it
+  // phases switched off for timing (results wrong): only in a build with -DWV_ABLATE (scripts/build_ablate.py wv:WV_ABLATE),
+  // the shipped loop tests nothing
+#ifdef WV_ABLATE
+  const int ablate = a.ablate;
+#else
+  constexpr int ablate = 0;
+#endif
   const int n = a.n, m = a.m, lpb = LPB > 0 ? LPB : a.lpb;
   constexpr int NPOS = 2 * NSTEP + 2;
   // LDS (doubles), compile-time offsets: the vectors sit at fixed distances from each other
@@ -582,7 +597,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   // Row / variable indices and scaling constants that only a checked iteration needs.  They are fetched from global memory
   // at the START of that iteration, in front of the sweeps, so that the round trip (L2 or HBM: 68 x 512 B per problem) runs
   // under the iteration's own arithmetic; kept for the whole solve they would cost ~170 registers.
-  const int pdense = (a.ablate & 32) ? 1 : a.pflag[b];         // P has entries off the three diagonals the compact constants hold
+  const int pdense = (ablate & 32) ? 1 : a.pflag[b];         // P has entries off the three diagonals the compact constants hold
   // delta_y (clipped) / delta_x of the checked iteration: kept in registers for the infeasibility certificates
   struct { double h[NS], b[NS], e[NS], r0[NV], var[NV], x; } dsv;
   // One pass over the lane's rows and variables.  MODE 0: initialise (right-hand side of the first iteration from the
@@ -817,12 +832,12 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   while (!status && iter < stop) {
     int next = stop;
     if (a.check > 0) { next = (iter / a.check + 1) * a.check; if (next > stop) next = stop; }
-    while (iter + 2 < next) { iter++; if (!(a.ablate & 1)) sweep(); if (!(a.ablate & 2)) rows(std::integral_constant<int, 1>{}); }
-    if (iter + 1 < next) { iter++; if (!(a.ablate & 1)) sweep(); if (!(a.ablate & 2)) rows(std::integral_constant<int, 1>{}); }
+    while (iter + 2 < next) { iter++; if (!(ablate & 1)) sweep(); if (!(ablate & 2)) rows(std::integral_constant<int, 1>{}); }
+    if (iter + 1 < next) { iter++; if (!(ablate & 1)) sweep(); if (!(ablate & 2)) rows(std::integral_constant<int, 1>{}); }
     iter++;
     c_ndy = 0.0; c_lhs = 0.0; c_ndx = 0.0; c_qdx = 0.0;
     sweep(); rows(std::integral_constant<int, 2>{});
-    if (a.ablate & 16) continue;
+    if (ablate & 16) continue;
     // ---- termination test (formulas of admm_check in sco_qp.hip) on the structured layout
     for (int approximate = 0; approximate < 2 && !status; approximate++) {
       if (approximate && iter < a.max_iter) break;
@@ -913,7 +928,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       //   dual:    || D^-1 P dx ||inf < c eps_dual_inf || D dx ||inf  and no row of E^-1 A dx leaves its finite bounds' cone
       // delta_y / delta_x of the checked iteration are in registers (dsv); column sums go through the two buffers the
       // test above has borrowed already.
-      if ((a.ablate & 64) == 0 && !prim_ok && ndy > epi && lhs < -epi * ndy) {
+      if ((ablate & 64) == 0 && !prim_ok && ndy > epi && lhs < -epi * ndy) {
         double nat = 0.0;
         {
           double part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -955,7 +970,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         nat = wv_wmax(nat);
         if (nat < epi * ndy) { status = approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE; break; }
       }
-      if ((a.ablate & 64) == 0 && !dual_ok && ndx > edi && qdx < -cscale * edi * ndx) {
+      if ((ablate & 64) == 0 && !dual_ok && ndx > edi && qdx < -cscale * edi * ndx) {
         // delta_x of the core variables takes the place of x in its block vector (the next checked pass rewrites it)
 #pragma unroll
         for (int v = 0; v < NV; v++) v_p[v][oXC - oXT] = dsv.var[v];
@@ -1093,7 +1108,11 @@ static void wv_fill_args(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, 
   a.Ap = d.Ap; a.Ai = d.Ai; a.Rp = d.Rp; a.Rj = d.Rj; a.Rpos = d.Rpos; a.Fp = d.Fp; a.Fi = d.Fi; a.Fpos = d.Fpos;
   a.x = d.x; a.y = d.y; a.resid = d.resid; a.status = d.status; a.iters = d.iters; a.prog = d.prog;
   a.sx = d.sx; a.sz = d.sz; a.sy = d.sy; a.st = d.st; a.sg = d.sg;
+#ifdef WV_ABLATE
   { const char *ab = getenv("SCO_WV_ABLATE"); a.ablate = ab ? atoi(ab) : 0; }
+#else
+  a.ablate = 0;
+#endif
 }
 
 // need[b] = the problem starts a QP, or it is active on a QP the wavefront tier factored (W buffer still holds S)

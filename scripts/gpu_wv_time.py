@@ -1,4 +1,7 @@
-"""Per-iteration time of the wavefront ADMM tier with phases switched off (dev script; SCO_WV_ABLATE: results wrong, timing only)."""
+"""Per-iteration time of the wavefront ADMM tier with phases switched off (dev script; SCO_WV_ABLATE: results wrong, timing only).
+
+The shipped kernel does not test SCO_WV_ABLATE: this script loads the variant library that does
+(`python scripts/build_ablate.py wv:WV_ABLATE` -> csrc/variants/libsco_ablate_wv_WV_ABLATE.so), or SCO_LIB_OVERRIDE."""
 import os, sys
 import numpy as np, scipy.sparse as sp
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -6,6 +9,10 @@ sys.argv = [sys.argv[0], "noop"]
 from sco_py_amd import _lib as L, _build
 if os.environ.get("SCO_LIB_OVERRIDE"):
     _build.LIB = os.environ["SCO_LIB_OVERRIDE"]; print("library", _build.LIB)
+else:
+    _build.LIB = os.path.join(_build.CSRC, "variants", "libsco_ablate_wv_WV_ABLATE.so"); print("library", _build.LIB)
+    if not os.path.exists(_build.LIB):
+        sys.exit("build the variant first: python scripts/build_ablate.py wv:WV_ABLATE")
 os.environ["SCO_WV_MIN_PER_CU"] = "0"     # every launch on the wavefront tier (default: > 3.3 problems per CU)
 import importlib.util
 spec = importlib.util.spec_from_file_location("wvc", os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_wv_check.py"))
