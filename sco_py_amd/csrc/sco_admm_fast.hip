@@ -20,7 +20,7 @@
 //     only the vectors that cross threads (x~, t, the eliminated right-hand side,
 //     the core right-hand side and solution) go through LDS;
 //   * HBM is read once (problem + W) and written once (answer).
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -85,49 +85,6 @@ bool fast_plan_build(const QpPlan &pl, FastHost &fh) {
 // --------------------------------------------------------------------------
 // device
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double fwmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double fwsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// maximum over the wavefront, valid in lane 63, by DPP row shifts / row broadcasts (see lwmax63 in sco_admm_rl.hip)
-__device__ __forceinline__ double fwmax63(double v) {
-  int lo, hi, lo2, hi2;
-#define FAST_DPP_MAX(ctrl, rmask)                                                            \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(lo, lo, ctrl, rmask, 0xf, false);                        \
-  hi2 = __builtin_amdgcn_update_dpp(hi, hi, ctrl, rmask, 0xf, false);                        \
-  v = fmax(v, __hiloint2double(hi2, lo2));
-  FAST_DPP_MAX(0x111, 0xf) FAST_DPP_MAX(0x112, 0xf) FAST_DPP_MAX(0x114, 0xf) FAST_DPP_MAX(0x118, 0xf)
-  FAST_DPP_MAX(0x142, 0xa) FAST_DPP_MAX(0x143, 0xc)
-#undef FAST_DPP_MAX
-  return v;
-}
-template <int NR, bool IS_MAX>
-__device__ __forceinline__ void fblock_reduce(double (&v)[NR], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? fwmax63(v[k]) : fwsum(v[k]);
-  __syncthreads();
-  if (lane == (IS_MAX ? 63 : 0)) {
-#pragma unroll
-    for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NR; k++) {
-    double r = red[k];
-#pragma unroll
-    for (int w = 1; w < FW; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
-    v[k] = r;
-  }
-}
-
 struct SellLds { const double *V; const unsigned short *I; int off, width; };
 
 // sum_k V[k] * vec[I[k]] over the calling thread's item (off = base[slice] + lane).
@@ -321,7 +278,7 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
     __syncthreads();
     if (!chk) continue;
 
-    // ---- termination test (same formulas as admm_check in sco_qp.hip) ----------------
+    // ---- termination test (the skeleton of osqp_check in sco_admm_check.h on this kernel's registers) ----
     const bool adapt_pt = a.adaptive && iter % a.ad_interval == 0 && iter < a.max_iter;
     double vs[7] = {0, 0, 0, 0, 0, 0, 0};         // adaptive rho: the same norms of the SCALED iterates
     for (int approximate = 0; approximate < 2 && !status; approximate++) {
@@ -329,8 +286,8 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
       const double *Ps = d.Ps + (size_t)b * d.nnzP;
       const double *Dg = d.D + (size_t)b * n, *Eg = d.E + (size_t)b * m;
       const double cinv = 1.0 / cscale;
-      double ea = a.eps_abs, er = a.eps_rel, epi = a.eps_prim_inf, edi = a.eps_dual_inf;
-      if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
+      const OsqpTol tol = osqp_tol(a.eps_abs, a.eps_rel, a.eps_prim_inf, a.eps_dual_inf, approximate);
+      const double ea = tol.ea, er = tol.er, epi = tol.epi, edi = tol.edi;
       double v[7] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int q = 0; q < NQ; q++)
@@ -350,7 +307,7 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
         v[3] = fabs(dj * (qj + px + aty)); v[4] = fabs(dj * qj); v[5] = fabs(dj * aty); v[6] = fabs(dj * px);
         if (adapt_pt) { vs[3] = fabs(qj + px + aty); vs[4] = fabs(qj); vs[5] = fabs(aty); vs[6] = fabs(px); }
       }
-      fblock_reduce<7, true>(v, red);
+      block_reduce<7, true, FW, true>(v, red);
       pri = v[0]; dua = cinv * v[3];
       if (!(pri <= SCO_INFTY) || !(dua <= SCO_INFTY)) { status = SCO_QP_NON_CVX; break; }
       const double eps_p = ea + er * fmax(v[1], v[2]);
@@ -362,21 +319,18 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
 #pragma unroll
         for (int q = 0; q < NQ; q++)
           if (R[q].on) {
-            double dy = sdy[R[q].i];
-            if (R[q].us > SCO_INFTY * SCO_MIN_SCALING) {
-              if (R[q].ls < -SCO_INFTY * SCO_MIN_SCALING) dy = 0.0; else dy = fmin(dy, 0.0);
-            } else if (R[q].ls < -SCO_INFTY * SCO_MIN_SCALING) dy = fmax(dy, 0.0);
+            const double dy = osqp_clip_dy(sdy[R[q].i], R[q].ls, R[q].us);
             sdy[R[q].i] = dy;
             r1[0] = fmax(r1[0], fabs(Eg[R[q].i] * dy));
           }
-        fblock_reduce<1, true>(r1, red);
+        block_reduce<1, true, FW, true>(r1, red);
         const double ndy = r1[0];
         if (ndy > epi) {
           double lhs[1] = {0.0};
 #pragma unroll
           for (int q = 0; q < NQ; q++)
             if (R[q].on) { const double dy = sdy[R[q].i]; lhs[0] += R[q].w * (R[q].us * fmax(dy, 0.0) + R[q].ls * fmin(dy, 0.0)); }
-          fblock_reduce<1, false>(lhs, red);
+          block_reduce<1, false, FW, true>(lhs, red);
           if (lhs[0] < -epi * ndy) {
             // A'(w dy): reuse swy as the weighted vector
             __syncthreads();
@@ -385,24 +339,24 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
             __syncthreads();
             double nat[1] = {0.0};
             if (colon) nat[0] = fabs(sell_dot<CW>(ac, swy) / Dg[j]);
-            fblock_reduce<1, true>(nat, red);
+            block_reduce<1, true, FW, true>(nat, red);
             // restore w*y for a possible second (approximate) pass
 #pragma unroll
             for (int q = 0; q < NQ; q++) if (R[q].on) swy[R[q].i] = R[q].w * R[q].y;
             __syncthreads();
-            if (nat[0] < epi * ndy) { status = approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE; break; }
+            if ((status = osqp_primal_inf_status(nat[0], ndy, epi, approximate))) break;
           }
         }
       }
       if (!dual_ok) {           // dual infeasibility certificate from delta_x
         double r1[1] = {0.0};
         if (colon) r1[0] = fabs(Dg[j] * sdx[j]);
-        fblock_reduce<1, true>(r1, red);
+        block_reduce<1, true, FW, true>(r1, red);
         const double ndx = r1[0];
         if (ndx > edi) {
           double qdx[1] = {0.0};
           if (colon) qdx[0] = qj * sdx[j];
-          fblock_reduce<1, false>(qdx, red);
+          block_reduce<1, false, FW, true>(qdx, red);
           if (qdx[0] < -cscale * edi * ndx) {
             double npx[1] = {0.0};
             if (colon) {
@@ -410,18 +364,17 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
               for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += Ps[d.Fpos[t]] * sdx[d.Fi[t]];
               npx[0] = fabs(px / Dg[j]);
             }
-            fblock_reduce<1, true>(npx, red);
+            block_reduce<1, true, FW, true>(npx, red);
             if (npx[0] < cscale * edi * ndx) {
               double bad[1] = {0.0};
 #pragma unroll
               for (int q = 0; q < NQ; q++)
                 if (R[q].on) {
                   const double adx = sell_dot<RW>(R[q].ar, sdx) / Eg[R[q].i];
-                  if ((R[q].us < SCO_INFTY * SCO_MIN_SCALING && adx > edi * ndx) ||
-                      (R[q].ls > -SCO_INFTY * SCO_MIN_SCALING && adx < -edi * ndx)) bad[0] = 1.0;
+                  if (osqp_row_leaves_cone(adx, R[q].ls, R[q].us, edi * ndx)) bad[0] = 1.0;
                 }
-              fblock_reduce<1, true>(bad, red);
-              if (bad[0] == 0.0) { status = approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE; break; }
+              block_reduce<1, true, FW, true>(bad, red);
+              if ((status = osqp_dual_inf_status(bad[0], approximate))) break;
             }
           }
         }
@@ -431,13 +384,9 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
     if (status) break;
     double rho_new = 0.0;
     if (adapt_pt) {
-      // OSQP's rho estimate (same rule as admm_rho_estimate in sco_qp.hip)
-      fblock_reduce<7, true>(vs, red);
-      const double rho = d.rho_b[b];
-      const double pn = vs[0] / (fmax(vs[1], vs[2]) + 1e-10);
-      const double dn = vs[3] / (fmax(vs[4], fmax(vs[5], vs[6])) + 1e-10);
-      const double est = fmin(fmax(rho * sqrt(pn / (dn + 1e-10)), SCO_RHO_MIN), 1e6);
-      if (est > rho * a.ad_tol || est < rho / a.ad_tol) rho_new = est;
+      block_reduce<7, true, FW, true>(vs, red);
+      const double rho = d.rho_b[b], est = osqp_rho_estimate(vs, rho);
+      if (osqp_rho_must_change(est, rho, a.ad_tol)) rho_new = est;
     }
     if (iter < a.max_iter && (rho_new > 0.0 || (a.slice > 0 && iter == it0 + a.slice))) {
       // rho must change or the slice is used up: park the solve

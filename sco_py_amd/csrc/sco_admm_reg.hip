@@ -23,7 +23,7 @@
 //     compile-time addresses;
 //   * kernel arguments are a slim struct (no SGPR spills in the loop);
 //   * r03: the solve parks and resumes like the other on-chip kernels (time slicing, adaptive rho).
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -151,36 +151,6 @@ struct RegArgs {
   int *prog, *rflag, *smask, *nupd;
   double *sx, *sz, *sy, *rho_b;
 };
-
-__device__ __forceinline__ double rwmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double rwsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-template <int NR, bool IS_MAX>
-__device__ __forceinline__ void rblock_reduce(double (&v)[NR], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? rwmax(v[k]) : rwsum(v[k]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NR; k++) {
-    double r = red[k];
-#pragma unroll
-    for (int w = 1; w < RWV; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
-    v[k] = r;
-  }
-}
 
 __device__ __forceinline__ double gat(const double *base, unsigned int byte_off) {
   return *(const double *)((const char *)base + byte_off);
@@ -376,7 +346,7 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
     __syncthreads();
     if (!chk) continue;
 
-    // ---- termination test (formulas of admm_check in sco_qp.hip) -------------------------
+    // ---- termination test (the skeleton of osqp_check in sco_admm_check.h on this kernel's registers) ----
     const bool adapt_pt = a.adaptive && iter % a.ad_interval == 0 && iter < a.max_iter;
     double vs[7] = {0, 0, 0, 0, 0, 0, 0};         // adaptive rho: the same norms of the SCALED iterates
     for (int approximate = 0; approximate < 2 && !status; approximate++) {
@@ -384,8 +354,8 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
       const double *Ps = a.Ps + (size_t)b * a.nnzP;
       const double *Dg = a.D + (size_t)b * n, *Eg = a.E + (size_t)b * m;
       const double cinv = 1.0 / cscale;
-      double ea = a.eps_abs, er = a.eps_rel, epi = a.eps_prim_inf, edi = a.eps_dual_inf;
-      if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
+      const OsqpTol tol = osqp_tol(a.eps_abs, a.eps_rel, a.eps_prim_inf, a.eps_dual_inf, approximate);
+      const double epi = tol.epi, edi = tol.edi;
       double v[7] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int q = 0; q < 2; q++)
@@ -405,33 +375,27 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
         v[3] = fabs(dj * (qj + px + aty)); v[4] = fabs(dj * qj); v[5] = fabs(dj * aty); v[6] = fabs(dj * px);
         if (adapt_pt) { vs[3] = fabs(qj + px + aty); vs[4] = fabs(qj); vs[5] = fabs(aty); vs[6] = fabs(px); }
       }
-      rblock_reduce<7, true>(v, s_red);
+      block_reduce<7, true, RWV>(v, s_red);
       pri = v[0]; dua = cinv * v[3];
-      if (!(pri <= SCO_INFTY) || !(dua <= SCO_INFTY)) { status = SCO_QP_NON_CVX; break; }
-      const double eps_p = ea + er * fmax(v[1], v[2]);
-      const double eps_d = ea + er * cinv * fmax(v[4], fmax(v[5], v[6]));
-      const bool prim_ok = (m == 0) || (pri < eps_p), dual_ok = dua < eps_d;
-      if (prim_ok && dual_ok) { status = approximate ? SCO_QP_SOLVED_INACCURATE : SCO_QP_SOLVED; break; }
+      bool prim_ok, dual_ok;
+      if ((status = osqp_converged(pri, dua, fmax(v[1], v[2]), fmax(v[4], fmax(v[5], v[6])), cinv, m, tol, approximate, prim_ok, dual_ok))) break;
       if (!prim_ok) {
         double r1[1] = {0.0};
 #pragma unroll
         for (int q = 0; q < 2; q++)
           if (r_on[q]) {
-            double dy = sdy[tid + q * RT];
-            if (r_us[q] > SCO_INFTY * SCO_MIN_SCALING) {
-              if (r_ls[q] < -SCO_INFTY * SCO_MIN_SCALING) dy = 0.0; else dy = fmin(dy, 0.0);
-            } else if (r_ls[q] < -SCO_INFTY * SCO_MIN_SCALING) dy = fmax(dy, 0.0);
+            const double dy = osqp_clip_dy(sdy[tid + q * RT], r_ls[q], r_us[q]);
             sdy[tid + q * RT] = dy;
             r1[0] = fmax(r1[0], fabs(Eg[tid + q * RT] * dy));
           }
-        rblock_reduce<1, true>(r1, s_red);
+        block_reduce<1, true, RWV>(r1, s_red);
         const double ndy = r1[0];
         if (ndy > epi) {
           double lhs[1] = {0.0};
 #pragma unroll
           for (int q = 0; q < 2; q++)
             if (r_on[q]) { const double dy = sdy[tid + q * RT]; lhs[0] += r_w[q] * (r_us[q] * fmax(dy, 0.0) + r_ls[q] * fmin(dy, 0.0)); }
-          rblock_reduce<1, false>(lhs, s_red);
+          block_reduce<1, false, RWV>(lhs, s_red);
           if (lhs[0] < -epi * ndy) {
             __syncthreads();
 #pragma unroll
@@ -439,23 +403,23 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
             __syncthreads();
             double nat[1] = {0.0};
             if (colon) nat[0] = fabs(reg_dot<CW>(vc, co, swy) / Dg[tid]);
-            rblock_reduce<1, true>(nat, s_red);
+            block_reduce<1, true, RWV>(nat, s_red);
 #pragma unroll
             for (int q = 0; q < 2; q++) if (r_on[q]) swy[tid + q * RT] = r_w[q] * r_y[q];
             __syncthreads();
-            if (nat[0] < epi * ndy) { status = approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE; break; }
+            if ((status = osqp_primal_inf_status(nat[0], ndy, epi, approximate))) break;
           }
         }
       }
       if (!dual_ok) {
         double r1[1] = {0.0};
         if (colon) r1[0] = fabs(Dg[tid] * sdx[tid]);
-        rblock_reduce<1, true>(r1, s_red);
+        block_reduce<1, true, RWV>(r1, s_red);
         const double ndx = r1[0];
         if (ndx > edi) {
           double qdx[1] = {0.0};
           if (colon) qdx[0] = qj * sdx[tid];
-          rblock_reduce<1, false>(qdx, s_red);
+          block_reduce<1, false, RWV>(qdx, s_red);
           if (qdx[0] < -cscale * edi * ndx) {
             double npx[1] = {0.0};
             if (colon) {
@@ -463,18 +427,17 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
               for (int t = a.Fp[tid]; t < a.Fp[tid + 1]; t++) px += Ps[a.Fpos[t]] * sdx[a.Fi[t]];
               npx[0] = fabs(px / Dg[tid]);
             }
-            rblock_reduce<1, true>(npx, s_red);
+            block_reduce<1, true, RWV>(npx, s_red);
             if (npx[0] < cscale * edi * ndx) {
               double bad[1] = {0.0};
 #pragma unroll
               for (int q = 0; q < 2; q++)
                 if (r_on[q]) {
                   const double adx = reg_dot<RW>(q ? vr1 : vr0, ro[q], sdx) / Eg[tid + q * RT];
-                  if ((r_us[q] < SCO_INFTY * SCO_MIN_SCALING && adx > edi * ndx) ||
-                      (r_ls[q] > -SCO_INFTY * SCO_MIN_SCALING && adx < -edi * ndx)) bad[0] = 1.0;
+                  if (osqp_row_leaves_cone(adx, r_ls[q], r_us[q], edi * ndx)) bad[0] = 1.0;
                 }
-              rblock_reduce<1, true>(bad, s_red);
-              if (bad[0] == 0.0) { status = approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE; break; }
+              block_reduce<1, true, RWV>(bad, s_red);
+              if ((status = osqp_dual_inf_status(bad[0], approximate))) break;
             }
           }
         }
@@ -484,13 +447,9 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
     if (status) break;
     double rho_new = 0.0;
     if (adapt_pt) {
-      // OSQP's rho estimate (same rule as admm_rho_estimate in sco_qp.hip)
-      rblock_reduce<7, true>(vs, s_red);
-      const double rho = a.rho_b[b];
-      const double pn = vs[0] / (fmax(vs[1], vs[2]) + 1e-10);
-      const double dn = vs[3] / (fmax(vs[4], fmax(vs[5], vs[6])) + 1e-10);
-      const double est = fmin(fmax(rho * sqrt(pn / (dn + 1e-10)), SCO_RHO_MIN), 1e6);
-      if (est > rho * a.ad_tol || est < rho / a.ad_tol) rho_new = est;
+      block_reduce<7, true, RWV>(vs, s_red);
+      const double rho = a.rho_b[b], est = osqp_rho_estimate(vs, rho);
+      if (osqp_rho_must_change(est, rho, a.ad_tol)) rho_new = est;
     }
     if (iter < a.max_iter && (rho_new > 0.0 || (a.slice > 0 && iter == it0 + a.slice))) {
       // rho must change or the slice is used up: park the solve

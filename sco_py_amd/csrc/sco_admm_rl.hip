@@ -22,7 +22,7 @@
 // Data placement as in sco_admm_reg.hip: W tile and packed byte offsets in
 // registers, sparse values in LDS sliced-ELL images built in thread order
 // (conflict-free, immediate offsets), padded slots gather an always-zero element.
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -526,32 +526,6 @@ struct RlArgs {
   double *stamp;     // diagnostic build only (SCO_STAMP), else unused
 };
 
-__device__ __forceinline__ double lwmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double lwsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// maximum over the wavefront, valid in lane 63: DPP row shifts and row broadcasts (VALU only; the shuffle version
-// goes through the LDS permute path six dependent times per value and made the termination test's reductions cost
-// 3.7 k cycles each, profiles/r01_check_stamps.txt).  A lane without a source keeps its own value, so a NaN
-// survives exactly when every lane holds one, as with the shuffles.
-__device__ __forceinline__ double lwmax63(double v) {
-  int lo, hi, lo2, hi2;
-#define RL_DPP_MAX(ctrl, rmask)                                                              \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(lo, lo, ctrl, rmask, 0xf, false);                        \
-  hi2 = __builtin_amdgcn_update_dpp(hi, hi, ctrl, rmask, 0xf, false);                        \
-  v = fmax(v, __hiloint2double(hi2, lo2));
-  RL_DPP_MAX(0x111, 0xf) RL_DPP_MAX(0x112, 0xf) RL_DPP_MAX(0x114, 0xf) RL_DPP_MAX(0x118, 0xf)
-  RL_DPP_MAX(0x142, 0xa) RL_DPP_MAX(0x143, 0xc)
-#undef RL_DPP_MAX
-  return v;
-}
 typedef unsigned int rl_uint2 __attribute__((ext_vector_type(2)));
 // Block maximum of six values with the lane-swap folds of the W reduction (fmax instead of add; fmax is idempotent, so
 // an odd value folds with itself): 17 swap / max instructions, then two row_shr scans instead of six.  After the folds
@@ -624,26 +598,6 @@ __device__ __forceinline__ void lblock_max6_sum2(double (&v)[8], double *red) {
   RL_ROW_STEP_ADD(sm, 0x111) RL_ROW_STEP_ADD(sm, 0x112) RL_ROW_STEP_ADD(sm, 0x114)
   v[0] = rl_bcast_lane(mx, 7); v[1] = rl_bcast_lane(mx, 15); v[2] = rl_bcast_lane(mx, 23); v[3] = rl_bcast_lane(mx, 31);
   v[4] = rl_bcast_lane(mx, 39); v[5] = rl_bcast_lane(mx, 47); v[6] = rl_bcast_lane(sm, 55); v[7] = rl_bcast_lane(sm, 63);
-}
-
-template <int NR, bool IS_MAX>
-__device__ __forceinline__ void lblock_reduce(double (&v)[NR], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? lwmax63(v[k]) : lwsum(v[k]);
-  __syncthreads();
-  if (lane == (IS_MAX ? 63 : 0)) {
-#pragma unroll
-    for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NR; k++) {
-    double r = red[k];
-#pragma unroll
-    for (int w = 1; w < LWV; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
-    v[k] = r;
-  }
 }
 
 __device__ __forceinline__ double lgat(const double *base, unsigned int byte_off) {
@@ -1345,7 +1299,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
                 if (cown >= 0) nat[0] = fabs(dv / Dg[RL_CVAR]);
               }
               if (eown >= 0) nat[0] = fmax(nat[0], fabs((r_ae[0] * (r_w[0] * dyp[0]) + r_ae[1] * (r_w[1] * dyp[1])) / Dg[RL_EVAR]));
-              lblock_reduce<1, true>(nat, s_red);
+              block_reduce<1, true, LWV, true>(nat, s_red);
 #pragma unroll
               for (int q = 0; q < NS; q++) if (r_p[q] >= 0) swy[r_p[q]] = r_w[q] * r_y[q];
               __syncthreads();
@@ -1368,7 +1322,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
                 const int pd = a.role[(size_t)12 * LT + tid];
                 if (pd >= 0) npx[0] = fmax(npx[0], fabs(Ps[pd] * dxe / Dg[RL_EVAR]));
               }
-              lblock_reduce<1, true>(npx, s_red);
+              block_reduce<1, true, LWV, true>(npx, s_red);
               if (npx[0] < cscale * edi * ndx) {
                 double bad[1] = {0.0};
                 double adc[NS];
@@ -1381,7 +1335,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
                     if ((r_us[q] < SCO_INFTY * SCO_MIN_SCALING && adx > edi * ndx) ||
                         (r_ls[q] > -SCO_INFTY * SCO_MIN_SCALING && adx < -edi * ndx)) bad[0] = 1.0;
                   }
-                lblock_reduce<1, true>(bad, s_red);
+                block_reduce<1, true, LWV, true>(bad, s_red);
                 if (bad[0] == 0.0) { status = approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE; break; }
               }
             }
@@ -1392,7 +1346,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
       CSTAMP(6)
       if (ADAPT && adapt_pt && !status) {
         // OSQP's rho estimate (compute_rho_estimate / adapt_rho of osqp 0.6, as recalled; oracle/osqp_ref.c)
-        lblock_reduce<7, true>(vs, s_red);
+        block_reduce<7, true, LWV, true>(vs, s_red);
         const double rho = a.rho_b[b];
         const double pn = vs[0] / (fmax(vs[1], vs[2]) + 1e-10);
         const double dn = vs[3] / (fmax(vs[4], fmax(vs[5], vs[6])) + 1e-10);

@@ -34,7 +34,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #define WV_T 64
 #ifndef WV_PD
@@ -287,6 +287,7 @@ __device__ __forceinline__ double wv_wred(double v) {
 }
 __device__ __forceinline__ double wv_wmax(double v) { return wv_wred<true>(v); }
 __device__ __forceinline__ double wv_wsum(double v) { return wv_wred<false>(v); }
+// the limit of upper_is_infinite / lower_is_infinite and osqp_row_leaves_cone (sco_admm_check.h): keep them one value
 #define WV_BIG (SCO_INFTY * SCO_MIN_SCALING)
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -689,7 +690,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         const double dy = x_rho * (zr - zn);
         x_y += dy; x_z = zn;
         if (MODE == 2) {
-          const double d1 = x_u > WV_BIG ? fmin(dy, 0.0) : dy, dc = x_l < -WV_BIG ? fmax(d1, 0.0) : d1;
+          const double d1 = upper_is_infinite(x_u) ? fmin(dy, 0.0) : dy, dc = lower_is_infinite(x_l) ? fmax(d1, 0.0) : d1;
           c_ndy = fmax(c_ndy, wv_recip(CKX) * fabs(dc)); c_lhs += x_w * (x_u * fmax(dc, 0.0) + x_l * fmin(dc, 0.0));
           dsv.x = dc;
         }
@@ -710,7 +711,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         const double xo = v_x[v], xn = alpha * xtc + oma * xo;
         v_x[v] = xn;
         if (MODE == 2) {
-          const double d1 = v_u[v] > WV_BIG ? fmin(dy, 0.0) : dy, dc = v_l[v] < -WV_BIG ? fmax(d1, 0.0) : d1;
+          const double d1 = upper_is_infinite(v_u[v]) ? fmin(dy, 0.0) : dy, dc = lower_is_infinite(v_l[v]) ? fmax(d1, 0.0) : d1;
           if (v_r0on[v]) { c_ndy = fmax(c_ndy, wv_recip(CKV(v, 1)) * fabs(dc)); c_lhs += v_u[v] * fmax(dc, 0.0) + v_l[v] * fmin(dc, 0.0); }
           dsv.r0[v] = dc;
           const double dx = xn - xo;
@@ -838,7 +839,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     c_ndy = 0.0; c_lhs = 0.0; c_ndx = 0.0; c_qdx = 0.0;
     sweep(); rows(std::integral_constant<int, 2>{});
     if (ablate & 16) continue;
-    // ---- termination test (formulas of admm_check in sco_qp.hip) on the structured layout
+    // ---- termination test (the decisions of sco_admm_check.h) on the structured layout
     for (int approximate = 0; approximate < 2 && !status; approximate++) {
       if (approximate && iter < a.max_iter) break;
       double ea = a.eps_abs, er = a.eps_rel, epi = a.eps_prim_inf, edi = a.eps_dual_inf;
@@ -923,7 +924,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       if (prim_ok && dual_ok) { status = approximate ? SCO_QP_SOLVED_INACCURATE : SCO_QP_SOLVED; break; }
       // The two infeasibility certificates, on the structured layout as well (r04: stiff penalty QPs -- the compounded
       // penalty of quirk Q1 -- meet their cheap preconditions at most checks; as generic loops over the CSC pattern in
-      // global memory they cost 8 % of the solve, scripts/gpu_wv_time.py).  Same quantities as admm_check in sco_qp.hip:
+      // global memory they cost 8 % of the solve, scripts/gpu_wv_time.py).  Same quantities as osqp_check in sco_admm_check.h:
       //   primal:  || D^-1 A' (w dy) ||inf < eps_prim_inf || E dy ||inf                  (dy clipped to the cone of the bounds)
       //   dual:    || D^-1 P dx ||inf < c eps_dual_inf || D dx ||inf  and no row of E^-1 A dx leaves its finite bounds' cone
       // delta_y / delta_x of the checked iteration are in registers (dsv); column sums go through the two buffers the
@@ -968,7 +969,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         }
         WV_SYNC();
         nat = wv_wmax(nat);
-        if (nat < epi * ndy) { status = approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE; break; }
+        if ((status = osqp_primal_inf_status(nat, ndy, epi, approximate))) break;
       }
       if ((ablate & 64) == 0 && !dual_ok && ndx > edi && qdx < -cscale * edi * ndx) {
         // delta_x of the core variables takes the place of x in its block vector (the next checked pass rewrites it)
@@ -1024,7 +1025,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
             if ((x_u < WV_BIG && adx > thr) || (x_l > -WV_BIG && adx < -thr)) badv = 1.0;
           }
           badv = wv_wmax(badv);
-          if (badv == 0.0) { status = approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE; break; }
+          if ((status = osqp_dual_inf_status(badv, approximate))) break;
         }
         WV_SYNC();
 #pragma unroll

@@ -18,7 +18,7 @@
 //     the dense core inverse W (L2 resident), and once to store the answer;
 //   * residual norms use wavefront shuffles + one LDS hop across the 4 waves;
 //   * no atomics, fixed summation orders: results are run-to-run deterministic.
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -60,44 +60,6 @@ extern "C" void sco_qp_default_settings(sco_qp_settings *s) {
 // device helpers
 // --------------------------------------------------------------------------
 #define NWAVE (SCO_BLOCK / 64)
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// Reduce NR per-thread values across the workgroup; every thread gets the
-// result.  `red` is NWAVE*NR doubles of LDS.  Fixed tree => deterministic.
-template <int NR, bool IS_MAX>
-__device__ __forceinline__ void block_reduce(double (&v)[NR], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? wave_max(v[k]) : wave_sum(v[k]);
-  __syncthreads();   // protect `red` against a previous use
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NR; k++) {
-    double r = red[k];
-#pragma unroll
-    for (int w = 1; w < NWAVE; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
-    v[k] = r;
-  }
-}
-
-__device__ __forceinline__ double limit_scaling(double v) {
-  v = v < SCO_MIN_SCALING ? 1.0 : v;
-  return v > SCO_MAX_SCALING ? SCO_MAX_SCALING : v;
-}
 
 __host__ __device__ __forceinline__ size_t tri_idx(int i, int j) {   // packed lower, j <= i
   return (size_t)i * (i + 1) / 2 + j;
@@ -189,12 +151,12 @@ __global__ __launch_bounds__(SCO_BLOCK) void qp_setup_kernel(SetupArgs a) {
     }
     {
       double s1[1] = {r2[0]};
-      block_reduce<1, false>(s1, red);
+      block_reduce<1, false, NWAVE>(s1, red);
       r2[0] = s1[0];
       double mq = 0.0;
       for (int j = tid; j < n; j += SCO_BLOCK) mq = fmax(mq, fabs(qs[j]));
       double s2[1] = {mq};
-      block_reduce<1, true>(s2, red);
+      block_reduce<1, true, NWAVE>(s2, red);
       r2[1] = s2[0];
     }
     double ct = n > 0 ? r2[0] / (double)n : 0.0;
@@ -524,122 +486,56 @@ __host__ __device__ inline size_t admm_lds_doubles(int n, int m, int nnzA, int n
   return (size_t)nnzA + n + 2 * (size_t)m + m + n + 2 * (size_t)m + m + n + n_e + 2 * (size_t)n_c + n_e + ncpl + m + n + NWAVE * 8;
 }
 
+// How qp_admm_kernel reaches rows, columns and dot products for osqp_check (sco_admm_check.h): thread t owns rows and
+// columns t, t + SCO_BLOCK, ...; CSR / CSC walks over the iterates in LDS
+struct AdmmOps {
+  const QpDev &d; const AdmmLds &s; const double *Ps, *Dg, *Eg;
+  template <class F> __device__ __forceinline__ void rows(F f) const { for (int i = threadIdx.x; i < d.m; i += SCO_BLOCK) f(i); }
+  template <class F> __device__ __forceinline__ void cols(F f) const { for (int j = threadIdx.x; j < d.n; j += SCO_BLOCK) f(j); }
+  __device__ __forceinline__ double row_dot(int i, const double *x) const {
+    double ax = 0.0;
+    for (int t = d.Rp[i]; t < d.Rp[i + 1]; t++) ax += s.As[d.Rpos[t]] * x[d.Rj[t]];
+    return ax;
+  }
+  __device__ __forceinline__ double p_dot(int j, const double *x) const {
+    double px = 0.0;
+    for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += Ps[d.Fpos[t]] * x[d.Fi[t]];
+    return px;
+  }
+  __device__ __forceinline__ double col_dot(int j, const double *y) const {
+    double aty = 0.0;
+    for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) { const int i = d.Ai[t]; aty += s.As[t] * y[i] * (double)s.w[i]; }
+    return aty;
+  }
+  __device__ __forceinline__ double Ax(int i) const { return row_dot(i, s.x); }
+  __device__ __forceinline__ double Adx(int i) const { return row_dot(i, s.sdx); }
+  __device__ __forceinline__ double Px(int j) const { return p_dot(j, s.x); }
+  __device__ __forceinline__ double Pdx(int j) const { return p_dot(j, s.sdx); }
+  __device__ __forceinline__ double Aty(int j) const { return col_dot(j, s.y); }
+  __device__ __forceinline__ double Atdy(int j) const { return col_dot(j, s.sdy); }
+  __device__ __forceinline__ double l(int i) const { return s.ls[i]; }
+  __device__ __forceinline__ double u(int i) const { return s.us[i]; }
+  __device__ __forceinline__ double w(int i) const { return (double)s.w[i]; }
+  __device__ __forceinline__ double z(int i) const { return s.z[i]; }
+  __device__ __forceinline__ double E(int i) const { return Eg[i]; }
+  __device__ __forceinline__ double dy(int i) const { return s.sdy[i]; }
+  __device__ __forceinline__ void set_dy(int i, double v) const { s.sdy[i] = v; }
+  __device__ __forceinline__ double q(int j) const { return s.qs[j]; }
+  __device__ __forceinline__ double D(int j) const { return Dg[j]; }
+  __device__ __forceinline__ double dx(int j) const { return s.sdx[j]; }
+};
+
 // Termination test of one ADMM iterate (all threads of the workgroup take part
 // and return the same value): 0 = keep iterating, otherwise an SCO_QP_* status.
 __device__ int admm_check(const AdmmArgs &a, const AdmmLds &s, int b, int approximate,
                           double cscale, double *pri_out, double *dua_out) {
   const QpDev &d = a.d;
-  const int tid = threadIdx.x, n = d.n, m = d.m;
-  const double *Ps = d.Ps + (size_t)b * d.nnzP;
-  const double *Dg = d.D + (size_t)b * n, *Eg = d.E + (size_t)b * m;
-  const double cinv = 1.0 / cscale;
-  double ea = a.eps_abs, er = a.eps_rel, epi = a.eps_prim_inf, edi = a.eps_dual_inf;
-  if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-
-  // rows: primal residual and its scale
-  double v[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int i = tid; i < m; i += SCO_BLOCK) {
-    double ax = 0.0;
-    for (int t = d.Rp[i]; t < d.Rp[i + 1]; t++) ax += s.As[d.Rpos[t]] * s.x[d.Rj[t]];
-    const double ei = 1.0 / Eg[i];
-    v[0] = fmax(v[0], fabs(ei * (ax - s.z[i])));
-    v[1] = fmax(v[1], fabs(ei * s.z[i]));
-    v[2] = fmax(v[2], fabs(ei * ax));
-  }
-  // columns: dual residual and its scale
-  for (int j = tid; j < n; j += SCO_BLOCK) {
-    double px = 0.0, aty = 0.0;
-    for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += Ps[d.Fpos[t]] * s.x[d.Fi[t]];
-    for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) { const int i = d.Ai[t]; aty += s.As[t] * s.y[i] * (double)s.w[i]; }
-    const double dj = 1.0 / Dg[j];
-    v[3] = fmax(v[3], fabs(dj * (s.qs[j] + px + aty)));
-    v[4] = fmax(v[4], fabs(dj * s.qs[j]));
-    v[5] = fmax(v[5], fabs(dj * aty));
-    v[6] = fmax(v[6], fabs(dj * px));
-  }
-  block_reduce<7, true>(v, s.red);
-  const double pri = v[0], dua = cinv * v[3];
-  *pri_out = pri; *dua_out = dua;
-  if (!(pri <= SCO_INFTY) || !(dua <= SCO_INFTY)) return SCO_QP_NON_CVX;
-  const double eps_p = ea + er * fmax(v[1], v[2]);
-  const double eps_d = ea + er * cinv * fmax(v[4], fmax(v[5], v[6]));
-  const bool prim_ok = (m == 0) || (pri < eps_p);
-  const bool dual_ok = dua < eps_d;
-  if (prim_ok && dual_ok) return approximate ? SCO_QP_SOLVED_INACCURATE : SCO_QP_SOLVED;
-
-  // ---- primal infeasibility certificate from delta_y --------------------------
-  if (!prim_ok) {
-    double r2[1] = {0.0};
-    for (int i = tid; i < m; i += SCO_BLOCK) {
-      double dy = s.sdy[i];
-      const double li = s.ls[i], ui = s.us[i];
-      if (ui > SCO_INFTY * SCO_MIN_SCALING) {
-        if (li < -SCO_INFTY * SCO_MIN_SCALING) dy = 0.0; else dy = fmin(dy, 0.0);
-      } else if (li < -SCO_INFTY * SCO_MIN_SCALING) dy = fmax(dy, 0.0);
-      s.sdy[i] = dy;
-      r2[0] = fmax(r2[0], fabs(Eg[i] * dy));
-    }
-    block_reduce<1, true>(r2, s.red);
-    const double ndy = r2[0];
-    if (ndy > epi) {
-      double lhs[1] = {0.0};
-      for (int i = tid; i < m; i += SCO_BLOCK) {
-        const double dy = s.sdy[i];
-        lhs[0] += (double)s.w[i] * (s.us[i] * fmax(dy, 0.0) + s.ls[i] * fmin(dy, 0.0));
-      }
-      block_reduce<1, false>(lhs, s.red);
-      if (lhs[0] < -epi * ndy) {
-        double nat[1] = {0.0};
-        for (int j = tid; j < n; j += SCO_BLOCK) {
-          double aty = 0.0;
-          for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) { const int i = d.Ai[t]; aty += s.As[t] * s.sdy[i] * (double)s.w[i]; }
-          nat[0] = fmax(nat[0], fabs(aty / Dg[j]));
-        }
-        block_reduce<1, true>(nat, s.red);
-        if (nat[0] < epi * ndy) return approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE;
-      }
-    }
-  }
-  // ---- dual infeasibility certificate from delta_x ------------------------------
-  if (!dual_ok) {
-    double r1[1] = {0.0};
-    for (int j = tid; j < n; j += SCO_BLOCK) r1[0] = fmax(r1[0], fabs(Dg[j] * s.sdx[j]));
-    block_reduce<1, true>(r1, s.red);
-    const double ndx = r1[0];
-    if (ndx > edi) {
-      double qdx[1] = {0.0};
-      for (int j = tid; j < n; j += SCO_BLOCK) qdx[0] += s.qs[j] * s.sdx[j];
-      block_reduce<1, false>(qdx, s.red);
-      if (qdx[0] < -cscale * edi * ndx) {
-        double npx[1] = {0.0};
-        for (int j = tid; j < n; j += SCO_BLOCK) {
-          double px = 0.0;
-          for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += Ps[d.Fpos[t]] * s.sdx[d.Fi[t]];
-          npx[0] = fmax(npx[0], fabs(px / Dg[j]));
-        }
-        block_reduce<1, true>(npx, s.red);
-        if (npx[0] < cscale * edi * ndx) {
-          double bad[1] = {0.0};
-          for (int i = tid; i < m; i += SCO_BLOCK) {
-            double adx = 0.0;
-            for (int t = d.Rp[i]; t < d.Rp[i + 1]; t++) adx += s.As[d.Rpos[t]] * s.sdx[d.Rj[t]];
-            adx /= Eg[i];
-            if ((s.us[i] < SCO_INFTY * SCO_MIN_SCALING && adx > edi * ndx) ||
-                (s.ls[i] > -SCO_INFTY * SCO_MIN_SCALING && adx < -edi * ndx)) bad[0] = 1.0;
-          }
-          block_reduce<1, true>(bad, s.red);
-          if (bad[0] == 0.0) return approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE;
-        }
-      }
-    }
-  }
-  return 0;
+  AdmmOps o{d, s, d.Ps + (size_t)b * d.nnzP, d.D + (size_t)b * d.n, d.E + (size_t)b * d.m};
+  return osqp_check<NWAVE>(o, osqp_tol(a.eps_abs, a.eps_rel, a.eps_prim_inf, a.eps_dual_inf, approximate), approximate, d.m, cscale, s.red, *pri_out, *dua_out);
 }
 
-// OSQP's rho estimate from the SCALED iterates in LDS (osqp 0.6 auxil.c compute_rho_estimate, as recalled; the
-// library is not available here, see oracle/osqp_ref.c):
-//   rho sqrt( (|Ax - z| / (max(|z|, |Ax|) + 1e-10)) / (|Px + q + A'y| / (max(|q|, |A'y|, |Px|) + 1e-10) + 1e-10) )
-// clipped to [1e-6, 1e6].  Fixed summation order: the value does not depend on scheduling.
+// The norms of the SCALED iterates in LDS for OSQP's rho estimate (osqp_rho_estimate), A'y as a (w y).  Fixed
+// summation order: the value does not depend on scheduling.
 __device__ double admm_rho_estimate(const AdmmArgs &a, const AdmmLds &s, int b, double rho) {
   const QpDev &d = a.d;
   const int tid = threadIdx.x, n = d.n, m = d.m;
@@ -657,10 +553,8 @@ __device__ double admm_rho_estimate(const AdmmArgs &a, const AdmmLds &s, int b, 
     v[3] = fmax(v[3], fabs(px + s.qs[j] + aty)); v[4] = fmax(v[4], fabs(s.qs[j]));
     v[5] = fmax(v[5], fabs(aty)); v[6] = fmax(v[6], fabs(px));
   }
-  block_reduce<7, true>(v, s.red);
-  const double pri = v[0] / (fmax(v[1], v[2]) + 1e-10);
-  const double dua = v[3] / (fmax(v[4], fmax(v[5], v[6])) + 1e-10);
-  return fmin(fmax(rho * sqrt(pri / (dua + 1e-10)), SCO_RHO_MIN), 1e6);
+  block_reduce<7, true, NWAVE>(v, s.red);
+  return osqp_rho_estimate(v, rho);
 }
 
 __global__ __launch_bounds__(SCO_BLOCK) void qp_admm_kernel(AdmmArgs a) {
@@ -770,7 +664,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void qp_admm_kernel(AdmmArgs a) {
     double rho_new = 0.0;
     if (a.adaptive && iter % a.ad_interval == 0 && iter < a.max_iter) {
       const double rho = d.rho_b[b], est = admm_rho_estimate(a, s, b, rho);
-      if (est > rho * a.ad_tol || est < rho / a.ad_tol) rho_new = est;
+      if (osqp_rho_must_change(est, rho, a.ad_tol)) rho_new = est;
     }
     if (rho_new > 0.0 || (a.slice > 0 && iter == it0 + a.slice && iter < a.max_iter)) {
       // rho must change (setup refactors, then the solve resumes), or the slice is used up (it ends on a

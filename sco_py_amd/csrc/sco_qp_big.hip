@@ -13,7 +13,7 @@
 //     the fall-back for cores that are not banded and the cross-check of the above.
 #include <type_traits>
 
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -61,39 +61,6 @@ bool big_plan_build(const QpPlan &pl, BigHost &bh) {
 // --------------------------------------------------------------------------
 // device helpers
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double bwmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double bwsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-template <int NR, bool IS_MAX, int NT = BT>
-__device__ __forceinline__ void bblock_reduce(double (&v)[NR], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? bwmax(v[k]) : bwsum(v[k]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NR; k++) {
-    double r = red[k];
-    for (int w = 1; w < NT / 64; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
-    v[k] = r;
-  }
-}
-__device__ __forceinline__ double blimit(double v) {
-  v = v < SCO_MIN_SCALING ? 1.0 : v;
-  return v > SCO_MAX_SCALING ? SCO_MAX_SCALING : v;
-}
-
 // chunk descriptor of the structured form (bt_plan_build): 16 ints per chunk
 #define CH_STRIDE 16      // kind, nact, ncols, r0, c0, pos0, col stride, e0, j0, r1, ep0, ep0 stride, ep1, ep1 stride, partial base, pad
 
@@ -151,12 +118,12 @@ __global__ __launch_bounds__(BT) void qp_setup_big_kernel(BigArgs a) {
       double v = 0.0;
       for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) v = fmax(v, fabs(Ps[d.Fpos[t]]));
       for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) v = fmax(v, fabs(As[t]));
-      Dt[j] = 1.0 / sqrt(blimit(v));
+      Dt[j] = 1.0 / sqrt(limit_scaling(v));
     }
     for (int i = tid; i < m; i += BT) {
       double v = 0.0;
       for (int t = d.Rp[i]; t < d.Rp[i + 1]; t++) v = fmax(v, fabs(As[d.Rpos[t]]));
-      Et[i] = 1.0 / sqrt(blimit(v));
+      Et[i] = 1.0 / sqrt(limit_scaling(v));
     }
     __syncthreads();
     for (int j = tid; j < n; j += BT) {
@@ -173,11 +140,11 @@ __global__ __launch_bounds__(BT) void qp_setup_big_kernel(BigArgs a) {
       for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) v = fmax(v, fabs(Ps[d.Fpos[t]]));
       s1[0] += v; s2[0] = fmax(s2[0], fabs(qs[j]));
     }
-    bblock_reduce<1, false>(s1, red);
-    bblock_reduce<1, true>(s2, red);
+    block_reduce<1, false, BWV>(s1, red);
+    block_reduce<1, true, BWV>(s2, red);
     double ct = n > 0 ? s1[0] / (double)n : 0.0;
-    ct = fmax(ct, blimit(s2[0]));
-    ct = 1.0 / blimit(ct);
+    ct = fmax(ct, limit_scaling(s2[0]));
+    ct = 1.0 / limit_scaling(ct);
     for (int t = tid; t < nnzP; t += BT) Ps[t] *= ct;
     for (int j = tid; j < n; j += BT) qs[j] *= ct;
     c *= ct;
@@ -391,9 +358,6 @@ __device__ __forceinline__ double big_row_core_dot(const QpDev &d, const double 
   return v;
 }
 
-// Termination test on the unscaled residuals + infeasibility certificates (formulas of
-// admm_check in sco_qp.hip); every thread of the workgroup calls it.  Returns the status
-// (0 = keep iterating).
 // Sparse dot products of the termination test with EIGHT entries in flight (r03).  One thread walks one row or column
 // (a core column of 12-DOF x 50 holds 105 entries) and every entry is an index load followed by the gather it addresses:
 // taken one at a time the walk is a chain of dependent memory round trips -- the test was 13 % of an iteration's time at
@@ -454,106 +418,53 @@ struct BigChk {
   const int *w;
   double cscale;
 };
+// How the global-memory kernels reach rows, columns and dot products for osqp_check (sco_admm_check.h): thread t owns
+// rows and columns t, t + NT, ...; A x, P x and A' (w y) with eight entries in flight, the certificates' sums one entry
+// at a time
+template <int NT>
+struct BigOps {
+  const QpDev &d; const BigChk &k;
+  template <class F> __device__ __forceinline__ void rows(F f) const { for (int i = threadIdx.x; i < d.m; i += NT) f(i); }
+  template <class F> __device__ __forceinline__ void cols(F f) const { for (int j = threadIdx.x; j < d.n; j += NT) f(j); }
+  __device__ __forceinline__ double Ax(int i) const { return big_row_dot8(d, k.As, k.x, d.Rp[i], d.Rp[i + 1]); }
+  __device__ __forceinline__ double Px(int j) const { return big_p_dot8(d, k.Ps, k.x, d.Fp[j], d.Fp[j + 1]); }
+  __device__ __forceinline__ double Aty(int j) const { return big_col_dot8<false>(d, k.As, k.y, k.w, d.Ap[j], d.Ap[j + 1]); }
+  __device__ __forceinline__ double Adx(int i) const {
+    double adx = 0.0;
+    for (int s = d.Rp[i]; s < d.Rp[i + 1]; s++) adx += k.As[d.Rpos[s]] * k.sdx[d.Rj[s]];
+    return adx;
+  }
+  __device__ __forceinline__ double Pdx(int j) const {
+    double px = 0.0;
+    for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += k.Ps[d.Fpos[t]] * k.sdx[d.Fi[t]];
+    return px;
+  }
+  __device__ __forceinline__ double Atdy(int j) const {
+    double aty = 0.0;
+    for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) { const int i = d.Ai[t]; aty += k.As[t] * k.sdy[i] * (double)k.w[i]; }
+    return aty;
+  }
+  __device__ __forceinline__ double l(int i) const { return k.ls[i]; }
+  __device__ __forceinline__ double u(int i) const { return k.us[i]; }
+  __device__ __forceinline__ double w(int i) const { return (double)k.w[i]; }
+  __device__ __forceinline__ double z(int i) const { return k.z[i]; }
+  __device__ __forceinline__ double E(int i) const { return k.Eg[i]; }
+  __device__ __forceinline__ double dy(int i) const { return k.sdy[i]; }
+  __device__ __forceinline__ void set_dy(int i, double v) const { k.sdy[i] = v; }
+  __device__ __forceinline__ double q(int j) const { return k.qs[j]; }
+  __device__ __forceinline__ double D(int j) const { return k.Dg[j]; }
+  __device__ __forceinline__ double dx(int j) const { return k.sdx[j]; }
+};
+
+// Termination test on the unscaled residuals + infeasibility certificates; every thread of the workgroup calls it.
+// Returns the status (0 = keep iterating).
 template <int NT>
 __device__ int big_check(const BigArgs &a, const BigChk &k, int iter, double *red, double &pri, double &dua) {
-  const QpDev &d = a.d;
-  const int tid = threadIdx.x, n = d.n, m = d.m;
-  const double *As = k.As, *Ps = k.Ps, *qs = k.qs, *ls = k.ls, *us = k.us, *Dg = k.Dg, *Eg = k.Eg;
-  const double *x = k.x, *y = k.y, *z = k.z, *sdx = k.sdx;
-  double *sdy = k.sdy;
-  const int *w = k.w;
-  const double cscale = k.cscale;
-  int status = 0;
-  for (int approximate = 0; approximate < 2 && !status; approximate++) {
-    if (approximate && iter < a.max_iter) break;
-    const double cinv = 1.0 / cscale;
-    double ea = a.eps_abs, er = a.eps_rel, epi = a.eps_prim_inf, edi = a.eps_dual_inf;
-    if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-    double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int i = tid; i < m; i += NT) {
-      const double ax = big_row_dot8(d, As, x, d.Rp[i], d.Rp[i + 1]);
-      const double ei = 1.0 / Eg[i];
-      v[0] = fmax(v[0], fabs(ei * (ax - z[i]))); v[1] = fmax(v[1], fabs(ei * z[i])); v[2] = fmax(v[2], fabs(ei * ax));
-    }
-    for (int j = tid; j < n; j += NT) {
-      const double px = big_p_dot8(d, Ps, x, d.Fp[j], d.Fp[j + 1]);
-      const double aty = big_col_dot8<false>(d, As, y, w, d.Ap[j], d.Ap[j + 1]);
-      const double dj = 1.0 / Dg[j];
-      v[3] = fmax(v[3], fabs(dj * (qs[j] + px + aty))); v[4] = fmax(v[4], fabs(dj * qs[j]));
-      v[5] = fmax(v[5], fabs(dj * aty)); v[6] = fmax(v[6], fabs(dj * px));
-    }
-    bblock_reduce<7, true, NT>(v, red);
-    pri = v[0]; dua = cinv * v[3];
-    if (!(pri <= SCO_INFTY) || !(dua <= SCO_INFTY)) { status = SCO_QP_NON_CVX; break; }
-    const double eps_p = ea + er * fmax(v[1], v[2]);
-    const double eps_d = ea + er * cinv * fmax(v[4], fmax(v[5], v[6]));
-    const bool prim_ok = (m == 0) || (pri < eps_p), dual_ok = dua < eps_d;
-    if (prim_ok && dual_ok) { status = approximate ? SCO_QP_SOLVED_INACCURATE : SCO_QP_SOLVED; break; }
-    if (!prim_ok) {
-      double r1[1] = {0.0};
-      for (int i = tid; i < m; i += NT) {
-        double dy = sdy[i];
-        if (us[i] > SCO_INFTY * SCO_MIN_SCALING) {
-          if (ls[i] < -SCO_INFTY * SCO_MIN_SCALING) dy = 0.0; else dy = fmin(dy, 0.0);
-        } else if (ls[i] < -SCO_INFTY * SCO_MIN_SCALING) dy = fmax(dy, 0.0);
-        sdy[i] = dy;
-        r1[0] = fmax(r1[0], fabs(Eg[i] * dy));
-      }
-      bblock_reduce<1, true, NT>(r1, red);
-      const double ndy = r1[0];
-      if (ndy > epi) {
-        double lhs[1] = {0.0};
-        for (int i = tid; i < m; i += NT) lhs[0] += (double)w[i] * (us[i] * fmax(sdy[i], 0.0) + ls[i] * fmin(sdy[i], 0.0));
-        bblock_reduce<1, false, NT>(lhs, red);
-        if (lhs[0] < -epi * ndy) {
-          double nat[1] = {0.0};
-          for (int j = tid; j < n; j += NT) {
-            double aty = 0.0;
-            for (int t = d.Ap[j]; t < d.Ap[j + 1]; t++) { const int i = d.Ai[t]; aty += As[t] * sdy[i] * (double)w[i]; }
-            nat[0] = fmax(nat[0], fabs(aty / Dg[j]));
-          }
-          bblock_reduce<1, true, NT>(nat, red);
-          if (nat[0] < epi * ndy) { status = approximate ? SCO_QP_PRIMAL_INFEASIBLE_INACCURATE : SCO_QP_PRIMAL_INFEASIBLE; break; }
-        }
-      }
-    }
-    if (!dual_ok) {
-      double r1[1] = {0.0};
-      for (int j = tid; j < n; j += NT) r1[0] = fmax(r1[0], fabs(Dg[j] * sdx[j]));
-      bblock_reduce<1, true, NT>(r1, red);
-      const double ndx = r1[0];
-      if (ndx > edi) {
-        double qdx[1] = {0.0};
-        for (int j = tid; j < n; j += NT) qdx[0] += qs[j] * sdx[j];
-        bblock_reduce<1, false, NT>(qdx, red);
-        if (qdx[0] < -cscale * edi * ndx) {
-          double npx[1] = {0.0};
-          for (int j = tid; j < n; j += NT) {
-            double px = 0.0;
-            for (int t = d.Fp[j]; t < d.Fp[j + 1]; t++) px += Ps[d.Fpos[t]] * sdx[d.Fi[t]];
-            npx[0] = fmax(npx[0], fabs(px / Dg[j]));
-          }
-          bblock_reduce<1, true, NT>(npx, red);
-          if (npx[0] < cscale * edi * ndx) {
-            double bad[1] = {0.0};
-            for (int i = tid; i < m; i += NT) {
-              double adx = 0.0;
-              for (int s = d.Rp[i]; s < d.Rp[i + 1]; s++) adx += As[d.Rpos[s]] * sdx[d.Rj[s]];
-              adx /= Eg[i];
-              if ((us[i] < SCO_INFTY * SCO_MIN_SCALING && adx > edi * ndx) ||
-                  (ls[i] > -SCO_INFTY * SCO_MIN_SCALING && adx < -edi * ndx)) bad[0] = 1.0;
-            }
-            bblock_reduce<1, true, NT>(bad, red);
-            if (bad[0] == 0.0) { status = approximate ? SCO_QP_DUAL_INFEASIBLE_INACCURATE : SCO_QP_DUAL_INFEASIBLE; break; }
-          }
-        }
-      }
-    }
-  }
-  return status;
+  BigOps<NT> o{a.d, k};
+  return osqp_check_at<NT / 64>(o, a, iter, a.d.m, k.cscale, red, pri, dua);
 }
 
-// OSQP's rho estimate from the SCALED iterates (same rule as admm_rho_estimate in sco_qp.hip)
+// The norms of the SCALED iterates for OSQP's rho estimate (osqp_rho_estimate), A'y as a (w y)
 template <int NT>
 __device__ double big_rho_estimate(const BigArgs &a, const BigChk &k, double *red, double rho) {
   const QpDev &d = a.d;
@@ -569,10 +480,8 @@ __device__ double big_rho_estimate(const BigArgs &a, const BigChk &k, double *re
     v[3] = fmax(v[3], fabs(px + k.qs[j] + aty)); v[4] = fmax(v[4], fabs(k.qs[j]));
     v[5] = fmax(v[5], fabs(aty)); v[6] = fmax(v[6], fabs(px));
   }
-  bblock_reduce<7, true, NT>(v, red);
-  const double pri = v[0] / (fmax(v[1], v[2]) + 1e-10);
-  const double dua = v[3] / (fmax(v[4], fmax(v[5], v[6])) + 1e-10);
-  return fmin(fmax(rho * sqrt(pri / (dua + 1e-10)), SCO_RHO_MIN), 1e6);
+  block_reduce<7, true, NT / 64>(v, red);
+  return osqp_rho_estimate(v, rho);
 }
 
 __global__ __launch_bounds__(BT) void qp_admm_big_kernel(BigArgs a) {
@@ -1667,7 +1576,7 @@ __global__ __launch_bounds__(BTT) void qp_admm_bt_kernel(BigArgs a) {
       status = big_check<BTT>(*ak, ck, iter, red, pri, dua);
       if (!status && ak->adaptive && iter % ak->ad_interval == 0 && iter < max_iter) {
         const double rho_b = d.rho_b[b], est = big_rho_estimate<BTT>(*ak, ck, red, rho_b);
-        if (est > rho_b * ak->ad_tol || est < rho_b / ak->ad_tol) rho_new = est;
+        if (osqp_rho_must_change(est, rho_b, ak->ad_tol)) rho_new = est;
       }
     }
     __syncthreads();

@@ -25,7 +25,7 @@
 // One workgroup of 256 threads per problem; problems are independent, so there is
 // no inter-workgroup communication.  The host only reads one "active problems"
 // counter per round.
-#include "sco_internal.h"
+#include "sco_admm_check.h"
 
 #include <algorithm>
 
@@ -156,24 +156,14 @@ struct sco_sqp {
 // --------------------------------------------------------------------------
 // device helpers
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
 // sums v[0..NS) and maxes v[NS..NS+NM) over the workgroup; result in every thread
 template <int NS, int NM>
 __device__ __forceinline__ void block_reduce_sm(double (&v)[NS + NM], double *red) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < NS; k++) v[k] = wsum(v[k]);
+  for (int k = 0; k < NS; k++) v[k] = wave_sum(v[k]);
 #pragma unroll
-  for (int k = NS; k < NS + NM; k++) v[k] = wmax(v[k]);
+  for (int k = NS; k < NS + NM; k++) v[k] = wave_max(v[k]);
   __syncthreads();
   if (lane == 0) {
 #pragma unroll
