@@ -75,15 +75,16 @@ typedef struct sco_qp_settings {
                                osqp_utils.py:195) | 1: start ADMM from the handle's previous solution
                                (x, y; z = A x), as OSQP's own warm start does.  NOT parity mode: iterates and
                                iteration counts change, the solution agrees to the QP tolerances.  Honoured by
-                               the row-local tier (the one 7-DOF x 20 runs on) and the structured global-memory
-                               tier (12-DOF x 50); the other tiers start cold.  */
+                               the row-local and wavefront tiers (the ones 7-DOF x 20 runs on) and the structured
+                               global-memory tier (12-DOF x 50); the other tiers start cold.  */
   int adaptive_rho;         /* osqp_utils.py:13  DEFAULT_ADAPTIVE_RHO = False (solver.py:39 lets the caller turn it on).
                                1: OSQP's rho update -- every adaptive_rho_interval iterations, after the termination
                                test, rho <- rho sqrt(normalised primal / normalised dual residual) clipped to
                                [1e-6, 1e6], taken when it leaves [rho / tol, rho tol]; the reduced system is then
                                refactored and the solve resumes from its iterates (the solve is parked and resumed
-                               around every update).  Runs on every on-chip tier and on the structured form of the
-                               global-memory tier; its dense form answers SCO_ERR_CAPACITY.  Not part of parity mode.  */
+                               around every update).  Runs on every on-chip tier (on the wavefront tier when SCO_WV_MIN_PER_CU
+                               is set: by default its launches stay on the row-local kernel, which is faster for them) and on
+                               the structured form of the global-memory tier; its dense form answers SCO_ERR_CAPACITY.  Not part of parity mode.  */
   int adaptive_rho_interval;/* 0 = 4 x check_termination (OSQP's value when it does not time itself: 100)         */
   double adaptive_rho_tolerance; /* OSQP default 5                                                                  */
 } sco_qp_settings;

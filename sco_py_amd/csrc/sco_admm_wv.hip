@@ -255,6 +255,10 @@ struct WvArgs {
   double *x, *y, *resid; int *status, *iters, *prog;
   double *sx, *sz, *sy, *st, *sg;
   int ablate;        // diagnostic (SCO_WV_ABLATE, read by builds with -DWV_ABLATE only): 1 = no sweeps, 2 = no row passes, 16 = no termination test behind the checked iteration, 64 = no infeasibility certificates (timing only, results wrong)
+  // the opt-in extensions (behind everything else: the fields above keep their places): warm = start from the handle's previous
+  // solution in x / y; ad_interval > 0 = adaptive rho (the ADAPT instantiation): rho is rho_b[b], estimated again every
+  // ad_interval iterations; when it must change the solve parks with the new value and smask[b] = rflag[b] = 1
+  int warm, ad_interval; double ad_tol; double *rho_b; int *rflag, *smask, *nupd;
 };
 
 // Wavefront-wide max / sum in registers: two DPP quad steps, two DPP mirror steps inside a 16-lane row, then the row and
@@ -305,7 +309,9 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
   const int *w = a.w + (size_t)b * m;
   const double *D = a.D + (size_t)b * n, *E = a.E + (size_t)b * m, *Ps = a.Ps + (size_t)b * a.nnzP;
   double *cst = a.cst + (size_t)b * a.cst_slots * 64;
-  // ---- value structure of a penalty QP (else the row-local kernel takes the problem)
+  // ---- value structure of a penalty QP (else the row-local kernel takes the problem); the base rho is the problem's own
+  // with adaptive rho (the setup kernel has just built d.rho from it)
+  const double rho_base = a.rho_b ? a.rho_b[b] : a.rho;
   int bad = 0, wk = 0, offd = 0;      // offd: P has entries inside a block off its diagonal
   for (int q = 0; q < NS; q++) { const int h = tab[(T.hrow + q) * 64 + lane]; if (h >= 0) wk = max(wk, w[h]); }
   wk = (int)wv_wmax((double)wk);
@@ -313,8 +319,8 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
     const int h = tab[(T.hrow + q) * 64 + lane], br = tab[(T.hbrow + q) * 64 + lane], ev = tab[(T.hevar + q) * 64 + lane];
     double eh = 0.0, eb = 0.0, de = 0.0;
     if (h >= 0) {
-      if (!(ls[h] < -WV_BIG) || rho[h] != a.rho || w[h] != wk) bad = 1;
-      if (!(us[br] > WV_BIG) || ls[br] != 0.0 || rho[br] != a.rho || w[br] != 1) bad = 1;
+      if (!(ls[h] < -WV_BIG) || rho[h] != rho_base || w[h] != wk) bad = 1;
+      if (!(us[br] > WV_BIG) || ls[br] != 0.0 || rho[br] != rho_base || w[br] != 1) bad = 1;
       eh = E[h]; eb = E[br]; de = D[ev];
     }
     double *c = cst + (size_t)wv_cst_h(q) * 64 + lane;
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
   for (int v = 0; v < NV; v++) {
     const int var = tab[(T.vvar + v) * 64 + lane], r0 = tab[(T.vrow + v) * 64 + lane];
     double *c = cst + (size_t)wv_cst_v(NS, v) * 64 + lane;
-    if (r0 >= 0 && (rho[r0] != a.rho || w[r0] != 1)) bad = 1;
+    if (r0 >= 0 && (rho[r0] != rho_base || w[r0] != 1)) bad = 1;
     c[0] = var >= 0 ? 1.0 / D[var] : 0.0;
     c[64] = r0 >= 0 ? 1.0 / E[r0] : 0.0;
     const int pm = tab[(T.vpm + v) * 64 + lane], pp = tab[(T.vpp + v) * 64 + lane];
@@ -462,8 +468,15 @@ __device__ __forceinline__ double wv_matvec(double acc, double w, const WvRow<BS
 template <typename T>
 __device__ __forceinline__ const T *wv_opaque(const T *p) { asm volatile("" : "+v"(p)); return p; }
 
-template <int BS, int NS, int NV, int NSTEP, int LPB>
+// EXT: the opt-in extensions, in instantiations of their own as in sco_admm_rl.hip: the default kernel (EXT = 0, parity mode)
+// holds no code of theirs.  Bit 0: the solve may start warm (WvArgs::warm); bit 1 (ADAPT): the adaptive-rho variant.
+// ADAPT: the problem's rho is rho_b[b]; at every ad_interval-th iteration, behind the termination test, the kernel forms
+// OSQP's estimate (osqp_rho_estimate, sco_admm_check.h) from norms that ride along in that test, and when rho must change it
+// parks the solve like a used-up slice.  The setup and factor kernels then run for the problem again (smask) and the next
+// launch resumes it: the right-hand side is rebuilt from x, z, y on every resume, so the new rho needs nothing further.
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
 __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
+  constexpr bool ADAPT = (EXT & 2) != 0;
   const int g = blockIdx.x, lane = threadIdx.x;
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
   if (b < 0 || (a.active && !a.active[b])) return;
@@ -492,7 +505,13 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
                 oXPK = oXPOS + 1;
   const double *As = a.As + (size_t)b * a.nnzA, *qs = a.qs + (size_t)b * n, *lsg = a.ls + (size_t)b * m, *usg = a.us + (size_t)b * m;
   const double *cstg0 = a.cst + (size_t)b * a.cst_slots * 64 + lane;
-  const double rho0 = a.rho, rinv0 = 1.0 / rho0, wc = a.wc[b], rw = wc * rho0;
+  double rho_in = a.rho;
+  if constexpr (ADAPT) {
+    rho_in = a.rho_b[b];
+    // (the row-local kernel behind this one skips the problems of this tier, ok[b]: each clears the flags of its own)
+    if (lane == 0) { a.rflag[b] = 0; a.smask[b] = 0; }
+  }
+  const double rho0 = rho_in, rinv0 = 1.0 / rho0, wc = a.wc[b], rw = wc * rho0;
   const double sigma = a.sigma, alpha = a.alpha, oma = 1.0 - alpha;
   const double cscale = a.cscale[b], cinv = 1.0 / cscale;
   const int it0 = a.slice > 0 ? a.prog[b] : 0;
@@ -825,12 +844,56 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     WV_SYNC();
   };
 
+  if ((EXT & 1) && a.warm && !resume) {
+    // OSQP-style warm start from the previous solution of this handle (x, y unscaled in a.x / a.y), the formulas of the
+    // row-local kernel:  x_s = x / D,  y_s = c y / (E w),  z = A_s x_s  (w: wc on the hinge rows, x_w on an extra row, 1 on
+    // the bound and box rows -- the value test).  The block's x goes through its vector in LDS: every lane of the block
+    // forms the products of its hinge rows from it.  rows(MODE 0) then builds the right-hand side as after a resume.
+    const double *Dg = a.D + (size_t)b * n, *Eg = a.E + (size_t)b * m;
+    const double *xg = a.x + (size_t)b * n, *yg = a.y + (size_t)b * m;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const int var = tab0[(oVVAR + v) * 64 + lane], r0 = tab0[(oVROW + v) * 64 + lane];
+      v_x[v] = var >= 0 ? xg[var] / Dg[var] : 0.0;
+      v_z[v] = v_a[v] * v_x[v];
+      v_y[v] = r0 >= 0 ? yg[r0] * cscale / Eg[r0] : 0.0;
+      v_p[v][oXC - oXT] = v_x[v];                  // (a lane without a variable: a zero into the dummy block)
+    }
+    WV_SYNC();
+    if (x_row >= 0) { x_z = x_a * x_p[oXC - oXT]; x_y = yg[x_row] * cscale / (Eg[x_row] * x_w); }
+    const double *xq = xt_p + (oXC - oXT);
+    const d2 a0 = *(const d2 *)xq, a1 = *(const d2 *)(xq + 2 * NPOS), a2 = *(const d2 *)(xq + 4 * NPOS), a3 = *(const d2 *)(xq + 6 * NPOS);
+    const double xc[8] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y, a3.x, a3.y};
+#pragma unroll
+    for (int q = 0; q < NS; q++) {
+      const int h = tab0[(oHROW + q) * 64 + lane], br = tab0[(oHBROW + q) * 64 + lane], ev = tab0[(oHEVAR + q) * 64 + lane];
+      double J[8];
+      if (JREG) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) J[k] = hJ[q][k];
+      } else {
+        const d2 *jp = (const d2 *)(jl_p + q * 512);
+        const d2 j0 = jp[0], j1 = jp[64], j2 = jp[128], j3 = jp[192];
+        J[0] = j0.x; J[1] = j0.y; J[2] = j1.x; J[3] = j1.y; J[4] = j2.x; J[5] = j2.y; J[6] = j3.x; J[7] = j3.y;
+      }
+      double s = J[0] * xc[0];
+#pragma unroll
+      for (int k = 1; k < BS; k++) s = __builtin_fma(J[k], xc[k], s);
+      if (h >= 0) {
+        h_xe[q] = xg[ev] / Dg[ev];
+        h_z[q] = s + h_ae[q] * h_xe[q]; h_zb[q] = h_ab[q] * h_xe[q];
+        h_y[q] = yg[h] * cscale / (Eg[h] * wc); h_yb[q] = yg[br] * cscale / Eg[br];
+      }
+    }
+    WV_SYNC();
+  }
   rows(std::integral_constant<int, 0>{});
 
   int status = 0, iter = it0;
   double pri = 0.0, dua = 0.0;
+  double rho_new = 0.0;       // ADAPT: > 0 = park now, this is the rho to continue with
   const int stop = (a.slice > 0 && it0 + a.slice < a.max_iter) ? it0 + a.slice : a.max_iter;
-  while (!status && iter < stop) {
+  while (!status && iter < stop && !(ADAPT && rho_new > 0.0)) {
     int next = stop;
     if (a.check > 0) { next = (iter / a.check + 1) * a.check; if (next > stop) next = stop; }
     while (iter + 2 < next) { iter++; if (!(ablate & 1)) sweep(); if (!(ablate & 2)) rows(std::integral_constant<int, 1>{}); }
@@ -839,6 +902,11 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     c_ndy = 0.0; c_lhs = 0.0; c_ndx = 0.0; c_qdx = 0.0;
     sweep(); rows(std::integral_constant<int, 2>{});
     if (ablate & 16) continue;
+    // ADAPT, at an update point: the norms of the SCALED iterates that osqp_rho_estimate takes ride along in the test.
+    // The estimate uses |z|, |Ax| and |q|, |A'y|, |Px| only through their maxima: four accumulators, not seven
+    // (v_pri = |Ax - z|, v_pn = max(|z|, |Ax|), v_dua = |Px + q + A'y|, v_dn = max(|q|, |A'y|, |Px|)).
+    const bool adapt_pt = ADAPT && iter % a.ad_interval == 0 && iter < a.max_iter;
+    double v_pri = 0.0, v_pn = 0.0, v_dua = 0.0, v_dn = 0.0;
     // ---- termination test (the decisions of sco_admm_check.h) on the structured layout
     for (int approximate = 0; approximate < 2 && !status; approximate++) {
       if (approximate && iter < a.max_iter) break;
@@ -873,6 +941,11 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
           const double aty = h_ae[q] * wy + h_ab[q] * h_yb[q];
           w_dua = fmax(w_dua, de * fabs(h_q[q] + aty));
           w_dn = fmax(w_dn, de * fmax(fabs(h_q[q]), fabs(aty)));
+          if (ADAPT && adapt_pt) {
+            v_pri = fmax(v_pri, fmax(fabs(ax - h_z[q]), fabs(axb - h_zb[q])));
+            v_pn = fmax(v_pn, fmax(fmax(fabs(h_z[q]), fabs(h_zb[q])), fmax(fabs(ax), fabs(axb))));
+            v_dua = fmax(v_dua, fabs(h_q[q] + aty)); v_dn = fmax(v_dn, fmax(fabs(h_q[q]), fabs(aty)));
+          }
 #pragma unroll
           for (int k = 0; k < BS; k++) part[k] = __builtin_fma(J[k], wy, part[k]);
         }
@@ -883,6 +956,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       {
         const double xcv = x_p[oXC - oXT], ax = x_a * xcv, ex = CKX;
         w_pri = fmax(w_pri, ex * fabs(ax - x_z)); w_pn = fmax(w_pn, ex * fmax(fabs(x_z), fabs(ax)));
+        if (ADAPT && adapt_pt) { v_pri = fmax(v_pri, fabs(ax - x_z)); v_pn = fmax(v_pn, fmax(fabs(x_z), fabs(ax))); }
         if (x_row >= 0) x_p[oEX - oXT] = x_a * (x_w * x_y);
       }
       WV_SYNC();
@@ -893,6 +967,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         const double dj = c[0], e0 = c[1];
         const double ax = v_a[v] * v_x[v];
         w_pri = fmax(w_pri, e0 * fabs(ax - v_z[v])); w_pn = fmax(w_pn, e0 * fmax(fabs(v_z[v]), fabs(ax)));
+        if (ADAPT && adapt_pt) { v_pri = fmax(v_pri, fabs(ax - v_z[v])); v_pn = fmax(v_pn, fmax(fabs(v_z[v]), fabs(ax))); }
         double aty = v_a[v] * v_y[v] + v_p[v][oEX - oXT];
         const double *pp = v_pp[v];
         if (LPB > 0) {
@@ -912,6 +987,10 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         if (v_on[v]) {
           w_dua = fmax(w_dua, dj * fabs(v_q[v] + px + aty));
           w_dn = fmax(w_dn, dj * fmax(fabs(v_q[v]), fmax(fabs(aty), fabs(px))));
+          if (ADAPT && adapt_pt) {
+            v_dua = fmax(v_dua, fabs(v_q[v] + px + aty));
+            v_dn = fmax(v_dn, fmax(fabs(v_q[v]), fmax(fabs(aty), fabs(px))));
+          }
         }
       }
       WV_SYNC();       // (the next pass over the rows rewrites the two buffers the test has borrowed)
@@ -1033,9 +1112,15 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         WV_SYNC();
       }
     }
+    if (ADAPT && adapt_pt && !status) {
+      const double vs[7] = {wv_wmax(v_pri), wv_wmax(v_pn), 0.0, wv_wmax(v_dua), wv_wmax(v_dn), 0.0, 0.0};    // (maxima of norms: 0 is neutral)
+      const double est = osqp_rho_estimate(vs, rho0);
+      if (osqp_rho_must_change(est, rho0, a.ad_tol)) rho_new = est;
+    }
   }
   if (!status && iter < a.max_iter) {
-    // the slice is used up: park the solve (scaled x, z, y in natural order; t', g_e and the right-hand side are rebuilt
+    if (ADAPT && rho_new > 0.0 && lane == 0) { a.rho_b[b] = rho_new; a.rflag[b] = 1; a.smask[b] = 1; a.nupd[b] += 1; }
+    // the slice is used up (or rho changes): park the solve (scaled x, z, y in natural order; t', g_e and the right-hand side are rebuilt
     // from them by the next launch with the same formulas, i.e. bit for bit).  t' and g_e are written too, in the form
     // the row-local kernel resumes from (sco_admm_rl.hip: t'_i = t_i - rw_i a_ie g_e): the SQP loop hands the tail of a
     // step, when fewer problems are alive than this tier needs to fill the chip, to that kernel.
@@ -1109,6 +1194,10 @@ static void wv_fill_args(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, 
   a.Ap = d.Ap; a.Ai = d.Ai; a.Rp = d.Rp; a.Rj = d.Rj; a.Rpos = d.Rpos; a.Fp = d.Fp; a.Fi = d.Fi; a.Fpos = d.Fpos;
   a.x = d.x; a.y = d.y; a.resid = d.resid; a.status = d.status; a.iters = d.iters; a.prog = d.prog;
   a.sx = d.sx; a.sz = d.sz; a.sy = d.sy; a.st = d.st; a.sg = d.sg;
+  a.warm = aa.warm; a.ad_interval = aa.adaptive ? aa.ad_interval : 0; a.ad_tol = aa.ad_tol;
+  // (null without adaptive rho: only the ADAPT instantiation and the factor kernel's value test read them)
+  a.rho_b = aa.adaptive ? d.rho_b : nullptr; a.rflag = aa.adaptive ? d.rflag : nullptr;
+  a.smask = aa.adaptive ? d.smask : nullptr; a.nupd = aa.adaptive ? d.nupd : nullptr;
 #ifdef WV_ABLATE
   { const char *ab = getenv("SCO_WV_ABLATE"); a.ablate = ab ? atoi(ab) : 0; }
 #else
@@ -1143,19 +1232,26 @@ int wv_launch_factor(const AdmmArgs &aa, const int *setup_mask, const WvHost &wh
   return SCO_OK;
 }
 
-template <int BS, int NS, int NV, int NSTEP, int LPB>
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
 static int wv_launch_k(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
   static bool attr_done[64] = {};
   int dev_ = 0;
   (void)hipGetDevice(&dev_);
   dev_ &= 63;
   if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     attr_done[dev_] = true;
   }
-  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB>), dim3(nwg), dim3(WV_T), lds, st, a);
+  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>), dim3(nwg), dim3(WV_T), lds, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
+}
+
+template <int BS, int NS, int NV, int NSTEP, int LPB>
+static int wv_launch_one(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
+  // parity mode runs the instantiation without any code of the extensions; the adaptive one can start warm as well
+  if (a.ad_interval > 0) return wv_launch_k<BS, NS, NV, NSTEP, LPB, 3>(a, nwg, lds, st);
+  return a.warm ? wv_launch_k<BS, NS, NV, NSTEP, LPB, 1>(a, nwg, lds, st) : wv_launch_k<BS, NS, NV, NSTEP, LPB, 0>(a, nwg, lds, st);
 }
 
 int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t st) {
@@ -1163,9 +1259,9 @@ int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t
   const int nwg = aa.d.nb > 0 ? aa.d.nb : aa.d.batch;
   // the LDS request also fixes how many problems share a CU: at most 4 (one wavefront per SIMD)
   const size_t lds = std::max(wh.lds_bytes, (size_t)36 * 1024);      // (36 KB: never a fifth workgroup on a CU)
-  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3) return wv_launch_k<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps
-  if (wh.NSTEP == 10 && wh.NS == 4) return wv_launch_k<7, 4, 3, 10, 0>(a, nwg, lds, st);
-  if (wh.NSTEP == 10) return wv_launch_k<8, 2, 2, 10, 0>(a, nwg, lds, st);
-  if (wh.NSTEP == 4) return wv_launch_k<8, 1, 1, 4, 0>(a, nwg, lds, st);
-  return wv_launch_k<8, 2, 2, 8, 0>(a, nwg, lds, st);
+  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3) return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps
+  if (wh.NSTEP == 10 && wh.NS == 4) return wv_launch_one<7, 4, 3, 10, 0>(a, nwg, lds, st);
+  if (wh.NSTEP == 10) return wv_launch_one<8, 2, 2, 10, 0>(a, nwg, lds, st);
+  if (wh.NSTEP == 4) return wv_launch_one<8, 1, 1, 4, 0>(a, nwg, lds, st);
+  return wv_launch_one<8, 2, 2, 8, 0>(a, nwg, lds, st);
 }

@@ -93,7 +93,7 @@ struct AdmmArgs {
   QpDev d;
   double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
   int max_iter, check;
-  int warm;     // start from the previous solution in d.x / d.y (row-local tier only)
+  int warm;     // start from the previous solution in d.x / d.y (row-local and wavefront kernels, structured global-memory tier)
   int slice;    // > 0: at most this many ADMM iterations per launch (row-local and generic kernels), see RlArgs
   int adaptive; // adaptive rho: every ad_interval iterations the kernel estimates rho; when it must change the solve
                 // parks with the new rho in d.rho_b[b] and d.smask[b] = d.rflag[b] = 1
@@ -258,7 +258,7 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
                          int slice, hipEvent_t mid, int *sliced, const QpGroup *grp = nullptr);
 bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st);
 int sco_qp_adaptive_interval(const sco_qp_settings *st);
-int sco_wv_min_live(int cus);      // fewest live problems for which a round runs on the wavefront tier
+int sco_wv_min_live(int cus, bool adaptive = false);      // fewest live problems for which a round runs on the wavefront tier
 bool sco_qp_has_wv(const sco_qp *qp, const sco_qp_settings *st);
 int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out);      // iterations run by the wavefront kernel since the reset
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st);   // the handle holds the wavefront tier and these settings can use it

@@ -21,6 +21,7 @@
 #include "sco_admm_check.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -846,8 +847,8 @@ static int qp_create_impl(sco_qp *qp, int device, int batch, int n, int m, const
   }
   {
     // wavefront tier (one wavefront per problem, block-tridiagonal core solve): patterns of trajectory penalty QPs; it
-    // needs the row-local tier beside it for problems whose values leave the penalty-QP structure, and for the opt-in
-    // extensions (warm start, adaptive rho), which stay on the row-local kernel
+    // needs the row-local tier beside it for problems whose values leave the penalty-QP structure.  The opt-in extensions
+    // (warm start, adaptive rho) run on it too
     const char *no_wv = getenv("SCO_QP_NO_WV");
     const bool want_wv = !(no_wv && no_wv[0] == '1');
     if (qp->use_rl && !qp->factor_cholesky && want_wv && wv_plan_build(pl, qp->wv)) {
@@ -932,11 +933,16 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
   return sco_qp_launch_sliced(qp, st, active_dev, active_dev, 0, mid, nullptr);
 }
 
-// fewest problems of a launch for which the wavefront tier is the faster one (SCO_WV_MIN_PER_CU: problems per CU, default 3.0)
-int sco_wv_min_live(int cus) {
+// fewest problems of a launch for which the wavefront tier is the faster one (SCO_WV_MIN_PER_CU: problems per CU, default 3.0).
+// With adaptive rho the default is "never": a launch then goes by the size of the BATCH, not by how many of its problems are
+// still alive (no round selection), a solve parks at every rho change and the launches are short and mostly narrow.  Measured
+// on `bench.py --beyond` (1024 problems, 4 per CU, 122 launches of ~100 iterations per step): 503 ms of ADMM launches per
+// step on this tier against 285 ms on the row-local kernel (profiles/wv_extensions.md).  The variable still applies when set.
+int sco_wv_min_live(int cus, bool adaptive) {
   const char *e = getenv("SCO_WV_MIN_PER_CU");
-  const double per = e ? atof(e) : 3.0;
-  return (int)(per * (cus > 0 ? cus : 256));
+  if (!e && adaptive) return INT_MAX;
+  const double live = (e ? atof(e) : 3.0) * (cus > 0 ? cus : 256);
+  return live >= (double)INT_MAX ? INT_MAX : (int)live;
 }
 
 int sco_qp_adaptive_interval(const sco_qp_settings *st) {
@@ -956,7 +962,7 @@ int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
   return SCO_OK;
 }
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st) { if (qp->use_wv) (void)hipMemsetAsync(qp->wvd.it_count, 0, sizeof(unsigned long long), st); }
-bool sco_qp_has_wv(const sco_qp *qp, const sco_qp_settings *st) { return qp->use_wv && !st->warm_start && !st->adaptive_rho; }
+bool sco_qp_has_wv(const sco_qp *qp, const sco_qp_settings *st) { (void)st; return qp->use_wv; }
 bool sco_qp_can_adapt(const sco_qp *qp) { return !(qp->use_big && !qp->use_bt); }
 
 // Launch windows and index lists (QpGroup) exist for the paths the bench workloads take: row-local ADMM kernel with
@@ -1003,12 +1009,14 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
   AdmmArgs aa{d, st->rho, st->sigma, st->alpha, st->eps_abs, st->eps_rel, st->eps_prim_inf, st->eps_dual_inf,
               st->max_iter, st->check_termination, (st->warm_start && qp->solved_once) ? 1 : 0, slice,
               adaptive ? 1 : 0, adaptive ? sco_qp_adaptive_interval(st) : 0, st->adaptive_rho_tolerance, nullptr};
-  // The wavefront tier runs cold-start, fixed-rho solves (parity mode); the opt-in extensions keep the row-local kernel.
+  // The wavefront tier runs parity mode and the opt-in extensions alike: a warm start only changes the start of a solve,
+  // adaptive rho runs its ADAPT instantiation, and the factorisation then runs over smask (dsetup.active), the problems
+  // that start a QP or have changed rho.
   // It puts four problems on a CU at ~3.1 us per iteration each where the row-local kernel runs one at ~0.95 us: it is
   // the faster way through a launch only with more than ~3 problems per CU to run (profiles/r04_wv.txt).  The SQP loop
   // says per round which one it wants (QpGroup::tier, from its live count); a plain sco_qp_solve goes by the batch.
-  const bool wv_can = qp->use_wv && !aa.warm && !adaptive && !st->warm_start;
-  const int wv_min = sco_wv_min_live(qp->cus);
+  const bool wv_can = qp->use_wv;
+  const int wv_min = sco_wv_min_live(qp->cus, adaptive);
   const bool wv_now = wv_can && (grp && grp->tier ? grp->tier == 2 : (grp ? grp->nb : d.batch) >= wv_min);
   qp->solved_once = true;
   if (!grp) SCO_HIP(hipEventRecord(qp->ev[0], stream));

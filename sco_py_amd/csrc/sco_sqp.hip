@@ -2030,14 +2030,15 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
   const bool select = slice_req > 0 && cus > 0 && s.batch > cus && sco_qp_supports_groups(h->qp1, &qsl) &&
                       !(sel_env && sel_env[0] == '0');
   if (getenv("SCO_SQP_TRACE_ROUNDS")) fprintf(stderr, "sco_sqp_solve: %d CUs, %d stream group(s), round selection %s, slice %d\n", cus, G, select ? "on" : "off", slice_req);
-  // Tier of a round (handles whose penalty QP has the wavefront tier, parity-mode settings): with at least wv_min live
+  // Tier of a round (handles whose penalty QP has the wavefront tier; warm-started QPs as in parity mode, adaptive rho has
+  // no round selection and reaches the tier through wv_plain below): with at least wv_min live
   // problems the round runs on the wavefront tier -- every live problem at once, four per CU -- below that on the row-local
   // kernel, one problem per CU in whole passes.  The first is the higher THROUGHPUT while the batch is alive (1024 / 3.1 us
   // against 256 / 0.95 us per iteration), the second the lower LATENCY for the tail of a step; a problem's QP changes kernel
   // at a slice boundary (the parked state is common).  Both kernels agree to rounding (1e-14), not bit for bit: for batches
   // that ever have wv_min live problems the last bits of a result depend on the schedule (SCO_WV_MIN_PER_CU=1e9: never).
   const bool has_wv = select && sco_qp_has_wv(h->qp1, &qsl);
-  const int wv_min = sco_wv_min_live(cus);
+  const int wv_min = sco_wv_min_live(cus, qsl.adaptive_rho != 0);
   h->groups_used = G;
   for (int g = 1; g < G; g++)
     if (!h->gstream[g - 1]) SCO_HIP(hipStreamCreate(&h->gstream[g - 1]));
