@@ -422,6 +422,15 @@ int sco_sqp_last_launches(const sco_sqp *h, int *launches, int *groups);
  * rest of sco_sqp_fetch's admm_iters sum, the projection QPs included); launches: rounds on either. */
 int sco_sqp_last_tiers(const sco_sqp *h, double ms[2], long long iters[2], int launches[2]);
 
+/* Mixed ADMM rounds (diagnostics).  A wavefront round with fewer live problems than the chip holds leaves CUs empty; the
+ * problems with most in front of them then run on the row-local kernel on those CUs, beside the wavefront launch
+ * (SCO_SQP_MIX=0 switches this off; scheduling only).  sco_debug_sqp_mixed: out[0] = mixed rounds of the last solve (they
+ * count as wavefront rounds above, and once more in launches[1]), out[1] = their side-window sizes summed.
+ * sco_debug_mix_split: the side-window size for `live` problems on `cus` CUs in `xcds` XCDs with `per_cu` wavefront
+ * problems per CU -- the largest k with ceil(k / xcds) + slack + ceil(ceil((live - k) / xcds) / per_cu) <= cus / xcds, or 0. */
+int sco_debug_sqp_mixed(const sco_sqp *h, int out[2]);
+int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu);
+
 /* Per-problem decision trace of the last solve, for stage-wise parity checks:
  * trace[batch][cap][8] = {kind, merit, model_merit, new_merit, trust, penalty,
  * qp_status, qp_iters}; n_entries[batch].  kind: 0 projection QP, 1 accepted step,

@@ -144,6 +144,7 @@ int rl_upload(const RlHost &rh, std::vector<void *> &allocs, RlDev &rd);
 int rl_launch(const AdmmArgs &a, const RlHost &rh, const RlDev &rd, hipStream_t st);
 
 // ---- wavefront tier (sco_admm_wv.hip): one wavefront per problem, block-tridiagonal core solve, four problems per CU
+#define SCO_WV_PER_CU 4       // (wv_launch's LDS request keeps a fifth workgroup off a CU: one wavefront per SIMD)
 struct WvHost {
   int bs = 0, nb = 0, mid = 0, lpb = 0, n_extra = 0;    // block order, blocks, middle block, lanes per block, second single rows
   int BS = 8, NS = 1, NV = 1, NSTEP = 4;                 // instantiation: mat-vec width, hinge-row / variable slots per lane, sweep steps
@@ -253,7 +254,16 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
 // the SQP loop; row-local tier with the Gauss-Jordan inversion only, see sco_qp_supports_groups)
 // tier: 0 = the handle decides (wavefront tier when the batch has at least SCO_WV_MIN_PER_CU problems per CU), 1 = row-local
 // kernel, 2 = wavefront tier (handles that hold it; others ignore the field)
-struct QpGroup { int b0, nb; hipStream_t stream; const int *list; int tier; };       // list: see QpDev (null = none)
+// kernel, 2 = wavefront tier (handles that hold it; others ignore the field), 3 = MIXED round (handles with the wavefront tier
+// and an index list): the problems list[side_b0 .. side_b0 + side_nb) run on the row-local kernel for side_slices slices on
+// side_stream, the rest of the window -- [b0, side_b0) and [side_b0 + side_nb, b0 + nb), one of them empty -- on the wavefront
+// tier on `stream`, both launches resident at once (the side window on CUs the wavefront launch leaves free); the streams
+// join before the call returns.  side_ev: three events of the caller's (no timing needed), not in use by an earlier round
+// that may still be in flight.
+struct QpGroup {                                                                      // list: see QpDev (null = none)
+  int b0, nb; hipStream_t stream; const int *list; int tier;
+  int side_b0 = 0, side_nb = 0, side_slices = 0; hipStream_t side_stream = nullptr; hipEvent_t side_ev[3] = {nullptr, nullptr, nullptr};
+};
 int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup_mask, const int *active_dev,
                          int slice, hipEvent_t mid, int *sliced, const QpGroup *grp = nullptr);
 bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st);

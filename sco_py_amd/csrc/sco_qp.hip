@@ -933,7 +933,10 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
   return sco_qp_launch_sliced(qp, st, active_dev, active_dev, 0, mid, nullptr);
 }
 
-// fewest problems of a launch for which the wavefront tier is the faster one (SCO_WV_MIN_PER_CU: problems per CU, default 3.0).
+// fewest problems of a launch for which the wavefront tier is the faster one (SCO_WV_MIN_PER_CU: problems per CU, default 2.75;
+// 3.0 until the SQP loop learnt mixed rounds, which fill the CUs such a round leaves free: on the 1024-problem 7x20 step 2.5 .. 3.0
+// give the same schedule and 2.0 and below a slower one, a step that starts with 700 problems is a quarter faster on this tier
+// (profiles/mixed_rounds.md) -- but the schedule tests pin a 700-problem batch, 2.73 per CU of 256, to row-local rounds).
 // With adaptive rho the default is "never": a launch then goes by the size of the BATCH, not by how many of its problems are
 // still alive (no round selection), a solve parks at every rho change and the launches are short and mostly narrow.  Measured
 // on `bench.py --beyond` (1024 problems, 4 per CU, 122 launches of ~100 iterations per step): 503 ms of ADMM launches per
@@ -941,7 +944,7 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
 int sco_wv_min_live(int cus, bool adaptive) {
   const char *e = getenv("SCO_WV_MIN_PER_CU");
   if (!e && adaptive) return INT_MAX;
-  const double live = (e ? atof(e) : 3.0) * (cus > 0 ? cus : 256);
+  const double live = (e ? atof(e) : 2.75) * (cus > 0 ? cus : 256);
   return live >= (double)INT_MAX ? INT_MAX : (int)live;
 }
 
@@ -1017,7 +1020,15 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
   // says per round which one it wants (QpGroup::tier, from its live count); a plain sco_qp_solve goes by the batch.
   const bool wv_can = qp->use_wv;
   const int wv_min = sco_wv_min_live(qp->cus, adaptive);
-  const bool wv_now = wv_can && (grp && grp->tier ? grp->tier == 2 : (grp ? grp->nb : d.batch) >= wv_min);
+  const bool mixed = grp && grp->tier == 3;
+  if (mixed) {
+    const bool at_end = grp->side_b0 == grp->b0 || grp->side_b0 + grp->side_nb == grp->b0 + grp->nb;
+    if (!wv_can || kern != K_RL || adaptive || slice <= 0 || !grp->list || grp->side_nb <= 0 || grp->side_nb >= grp->nb || !at_end ||
+        grp->side_slices <= 0 || !grp->side_stream || !grp->side_ev[0] || !grp->side_ev[1] || !grp->side_ev[2]) {
+      sco_set_error("sco_qp_launch_sliced: mixed round not supported by this handle or its side window is malformed"); return SCO_ERR_STATE;
+    }
+  }
+  const bool wv_now = wv_can && (grp && grp->tier ? grp->tier >= 2 : (grp ? grp->nb : d.batch) >= wv_min);
   qp->solved_once = true;
   if (!grp) SCO_HIP(hipEventRecord(qp->ev[0], stream));
   if (adaptive && setup_mask != SCO_MASK_NONE) {
@@ -1041,8 +1052,15 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
     SCO_HIP(hipGetLastError());
     if (wv_now) {
       // twisted block factorisation + the value test; the dense inverse below then runs for the problems that failed it only
+      // (mixed round: for every problem of the window that starts a QP, the side window's too, while the W buffer still holds
+      // S -- a problem that starts its QP on the row-local side keeps its factor G and may run on this tier in a later round)
       int r_ = wv_launch_factor(aa, dsetup.active, qp->wv, qp->wvd, stream);
       if (r_) return r_;
+      if (mixed) {
+        // the side window's problems that start a QP, or whose QP this tier factored (W not formed yet): dense inverse below
+        AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb;
+        if ((r_ = wv_launch_need(as, dsetup.active, qp->wvd, stream))) return r_;
+      }
       dsetup.active = qp->wvd.rl_need;
     } else if (qp->use_wv) {
       // a row-local launch on a handle that also runs the wavefront tier: besides the problems that start a QP, the dense
@@ -1063,7 +1081,26 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
   }
   if (!grp) SCO_HIP(hipEventRecord(qp->ev[1], stream));
   if (mid) SCO_HIP(hipEventRecord(mid, stream));
-  if (kern == K_RL) {
+  if (kern == K_RL && mixed) {
+    // Two launches resident at once.  A row-local workgroup needs a whole CU and finds none once the wavefront launch has
+    // spread over the chip, so the side launch is issued first and the wavefront launch is gated behind an event recorded
+    // in front of it: it cannot be dispatched before the side stream has reached its launch.  Neither launch reads what the
+    // other writes (disjoint problems), so neither can wait for the other; both streams join below.
+    AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb; as.slice = grp->side_slices * slice;
+    AdmmArgs aw = aa;
+    aw.d.b0 = grp->side_b0 == grp->b0 ? grp->b0 + grp->side_nb : grp->b0; aw.d.nb = grp->nb - grp->side_nb;
+    SCO_HIP(hipEventRecord(grp->side_ev[0], stream));
+    SCO_HIP(hipStreamWaitEvent(grp->side_stream, grp->side_ev[0], 0));
+    SCO_HIP(hipEventRecord(grp->side_ev[1], grp->side_stream));
+    int r_ = rl_launch(as, qp->rl, qp->rld, grp->side_stream);
+    if (r_) return r_;
+    SCO_HIP(hipEventRecord(grp->side_ev[2], grp->side_stream));
+    SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[1], 0));
+    if ((r_ = wv_launch(aw, qp->wv, qp->wvd, stream))) return r_;
+    aw.skip = qp->wvd.ok;                        // the problems of the wavefront window that failed the value test
+    if ((r_ = rl_launch(aw, qp->rl, qp->rld, stream))) return r_;
+    SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[2], 0));
+  } else if (kern == K_RL) {
     if (wv_now) {
       int r_ = wv_launch(aa, qp->wv, qp->wvd, stream);
       if (r_) return r_;

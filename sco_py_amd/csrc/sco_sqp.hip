@@ -52,6 +52,7 @@ struct SqpScalars {
 
 #define SQP_MAX_GROUPS 4
 #define SQP_DEPTH 2        // rounds kept in flight per stream group
+#define SQP_MIX_DEFAULT 1  // mixed ADMM rounds (SCO_SQP_MIX): on
 
 struct SqpDev {
   int b0;            // launch window of a stream group: workgroup g of the round kernels works on problem b0 + g
@@ -151,6 +152,8 @@ struct sco_sqp {
   int launches = 0;        // round launches over all stream groups
   int wv_rounds = 0;       // of them on the wavefront tier
   double wv_ms = 0.0;      // ADMM time of those rounds (part of last_ms[2])
+  int mixed_rounds = 0, mixed_side = 0;   // of the wavefront rounds the mixed ones, and their side-window sizes summed
+  std::vector<hipEvent_t> mix_events;     // three per mixed round (QpGroup::side_ev), no timing
 };
 
 // --------------------------------------------------------------------------
@@ -1518,6 +1521,7 @@ extern "C" int sco_sqp_destroy(sco_sqp *h) {
   for (auto e : h->events) (void)hipEventDestroy(e);
   for (auto &ge : h->gevents) for (auto e : ge) (void)hipEventDestroy(e);
   for (auto e : h->done) (void)hipEventDestroy(e);
+  for (auto e : h->mix_events) (void)hipEventDestroy(e);
   for (auto gs : h->gstream) if (gs) { (void)hipStreamSynchronize(gs); (void)hipStreamDestroy(gs); }
   if (h->host_active) (void)hipHostFree(h->host_active);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1834,11 +1838,13 @@ static hipEvent_t next_event(sco_sqp *h, size_t &cursor) {
 // result is unchanged, only the round it happens in moves (model on the measured chains, 1024 problems at 7x20:
 // 667 -> 636 ms per step; choosing by the true remaining work would give 629, profiles/r02_slice_model.txt).
 // n_active starts the round at the number of live problems left out (sqp_post_kernel adds those that ran and go on).
+// `order` (mixed rounds, at most SEL_T listed problems): the list is then sorted by that estimate, most in front first, ties by
+// index -- its head is the side window of the round.
 #define SEL_T 1024
 #define SEL_BUCKETS 1024
 // (r03: the kernel works on the problems [s.b0, s.b0 + nb) of a stream group and fills that group's part of the list, so
 // selection and stream groups combine: SCO_SQP_GROUPS)
-__global__ __launch_bounds__(SEL_T) void sqp_select_kernel(SqpDev s, QpDev q1, int cus, int slice, int max_iter, int cap, int nb) {
+__global__ __launch_bounds__(SEL_T) void sqp_select_kernel(SqpDev s, QpDev q1, int cus, int slice, int max_iter, int cap, int nb, int order) {
   __shared__ int hist[SEL_BUCKETS];
   __shared__ int part[SEL_T], part2[SEL_T];
   __shared__ int s_active, s_thr, s_take;
@@ -1901,6 +1907,17 @@ __global__ __launch_bounds__(SEL_T) void sqp_select_kernel(SqpDev s, QpDev q1, i
     if (r) list[pos++] = b;
   }
   for (int g = quota + tid; g < cap; g += SEL_T) list[g] = -1;
+  if (order && quota <= SEL_T) {
+    // rank of every listed problem among the listed ones by (bucket, position): a stable counting sort, one problem per thread
+    __syncthreads();
+    const int mine_b = tid < quota ? list[tid] : -1, mine_k = tid < quota ? key_of(mine_b) : SEL_BUCKETS;
+    part[tid] = mine_k;
+    __syncthreads();
+    int rank = 0;
+    for (int j = 0; j < quota; j++) { const int kj = part[j]; rank += (kj < mine_k || (kj == mine_k && j < tid)) ? 1 : 0; }
+    __syncthreads();
+    if (tid < quota) list[rank] = mine_b;
+  }
 }
 
 // problems the host loop's launch cap left unfinished: failed + SCO_SQP_FLAG_CAPPED
@@ -1909,6 +1926,17 @@ __global__ void sqp_cap_kernel(SqpDev s) {
   if (b >= s.batch) return;
   SqpScalars &sc = s.sc[b];
   if (sc.state != ST_DONE) { sc.state = ST_DONE; sc.success = 0; sc.flags |= SCO_SQP_FLAG_CAPPED; s.active[b] = 0; }
+}
+
+// XCDs the device deals the workgroups of a launch to (qp_mix_split).  HIP has no attribute for it: eight on the CDNA3 / CDNA4
+// parts whose CU count they divide, else one; SCO_SQP_XCDS overrides.
+static int sqp_xcds(int device, int cus) {
+  const char *e = getenv("SCO_SQP_XCDS");
+  if (e && atoi(e) > 0) return atoi(e);
+  hipDeviceProp_t pr;
+  if (hipGetDeviceProperties(&pr, device) != hipSuccess) { (void)hipGetLastError(); return 1; }
+  const bool multi = !strncmp(pr.gcnArchName, "gfx94", 5) || !strncmp(pr.gcnArchName, "gfx95", 5);
+  return (multi && cus > 0 && cus % 8 == 0) ? 8 : 1;
 }
 
 extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs) {
@@ -2039,6 +2067,22 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
   // that ever have wv_min live problems the last bits of a result depend on the schedule (SCO_WV_MIN_PER_CU=1e9: never).
   const bool has_wv = select && sco_qp_has_wv(h->qp1, &qsl);
   const int wv_min = sco_wv_min_live(cus, qsl.adaptive_rho != 0);
+  // MIXED rounds (SCO_SQP_MIX, one stream group, fixed rho): a wavefront round with fewer live problems than the chip holds
+  // leaves CUs empty.  The k problems with most in front of them -- the head of the round's list, which sqp_select_kernel then
+  // sorts -- run on the row-local kernel on those CUs instead, mix_slices slices in the time of one wavefront slice, beside the
+  // wavefront launch over the rest of the list (sco_qp_launch_sliced, tier 3; k: qp_mix_split).  Per problem the sequence of QPs
+  // and every decision is unchanged; which kernel runs a given slice moves, as at wv_min.  SCO_SQP_MIX_PICK=tail (test hook)
+  // takes the side window from the end of the list in odd rounds, so that problems change sides in both directions.
+  auto env_int = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+  const bool mix_on = has_wv && G == 1 && !qsl.adaptive_rho && env_int("SCO_SQP_MIX", SQP_MIX_DEFAULT) != 0;
+  const int mix_slack = std::max(0, env_int("SCO_SQP_MIX_SLACK", 1)), mix_slices = std::max(1, env_int("SCO_SQP_MIX_SLICES", 2));
+  const int xcds = mix_on ? sqp_xcds(h->device, cus) : 1;
+  bool mix_tail = false;
+  { const char *pe = getenv("SCO_SQP_MIX_PICK"); mix_tail = pe && !strcmp(pe, "tail"); }
+  if (mix_on && !h->gstream[0]) SCO_HIP(hipStreamCreate(&h->gstream[0]));
+  size_t mix_ec = 0;
+  int mixed_rounds = 0, mixed_side = 0;
+  std::vector<int> round_k;                     // per round of group 0: -1 row-local, 0 wavefront, k > 0 mixed (SCO_SQP_TRACE_ROUNDS)
   h->groups_used = G;
   for (int g = 1; g < G; g++)
     if (!h->gstream[g - 1]) SCO_HIP(hipStreamCreate(&h->gstream[g - 1]));
@@ -2070,12 +2114,17 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
     sg.list = nullptr;
     int nwg = r.nb;                              // workgroups of this round's kernels
     const bool wv_round = has_wv && r.last_active >= wv_min;
+    int mix_k = 0;                               // side window of a mixed round
     if (select) {
       // compact launch: as many workgroups as the selection can let run, sized from the newest active count the host has
       // (a pass of the chip = one problem per CU, four on the wavefront tier)
       const int pass = wv_round ? 4 * cus : cus;
       nwg = std::max(1, r.last_active <= pass ? r.last_active : (r.last_active / pass) * pass);
-      hipLaunchKernelGGL(sqp_select_kernel, dim3(1), dim3(SEL_T), 0, r.st, sg, h->qp1->d, pass, slice_req, qsl.max_iter, nwg, r.nb);
+      if (mix_on && wv_round && r.last_active < SCO_WV_PER_CU * cus && nwg <= SEL_T) {
+        mix_k = qp_mix_split(r.last_active, cus, xcds, mix_slack, SCO_WV_PER_CU);
+        if (mix_k >= nwg) mix_k = 0;
+      }
+      hipLaunchKernelGGL(sqp_select_kernel, dim3(1), dim3(SEL_T), 0, r.st, sg, h->qp1->d, pass, slice_req, qsl.max_iter, nwg, r.nb, mix_k > 0 ? 1 : 0);
       SCO_HIP(hipGetLastError());
       sg.list = s.list_buf;
     }
@@ -2086,7 +2135,17 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
     SCO_HIP(hipGetLastError());
     gmark(g, 0);
     hipEvent_t gm = gevent(g); r.stage.push_back(1);
-    const QpGroup win{r.b0, nwg, r.st, sg.list, has_wv ? (wv_round ? 2 : 1) : 0};
+    QpGroup win{r.b0, nwg, r.st, sg.list, has_wv ? (wv_round ? 2 : 1) : 0};
+    if (mix_k > 0) {
+      win.tier = 3; win.side_nb = mix_k; win.side_slices = mix_slices; win.side_stream = h->gstream[0];
+      win.side_b0 = r.b0 + ((mix_tail && (r.issued & 1)) ? nwg - mix_k : 0);
+      for (int e = 0; e < 3; e++) {
+        if (mix_ec == h->mix_events.size()) { hipEvent_t ev; SCO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); h->mix_events.push_back(ev); }
+        win.side_ev[e] = h->mix_events[mix_ec++];
+      }
+      mixed_rounds++; mixed_side += mix_k;
+    }
+    if (g == 0) round_k.push_back(mix_k > 0 ? mix_k : (wv_round ? 0 : -1));
     // without round selection (at most one problem per CU) the launch itself goes by its size (sco_qp_launch_sliced): with
     // SCO_WV_MIN_PER_CU lowered such a round runs on the wavefront tier too, and is counted as one
     const bool wv_plain = !has_wv && sco_qp_has_wv(h->qp1, &qsl) && nwg >= wv_min;
@@ -2128,8 +2187,13 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
         SCO_HIP(hipEventSynchronize(done[(size_t)g * SQP_DEPTH + slot]));
         r.last_active = h->host_active[g * SQP_DEPTH + slot];
         r.retired++;
-        if (getenv("SCO_SQP_TRACE_ROUNDS") && (r.retired < 40 || r.retired % 100 == 0))
-          fprintf(stderr, "sco_sqp_solve: group %d round %d, %d problems active\n", g, r.retired, r.last_active);
+        if (getenv("SCO_SQP_TRACE_ROUNDS") && (r.retired < 40 || r.retired % 100 == 0 || atoi(getenv("SCO_SQP_TRACE_ROUNDS")) >= 2)) {   // (2: every round)
+          const int rk = (g == 0 && has_wv) ? round_k[r.retired - 1] : -2;
+          char kind[48] = "";
+          if (rk > 0) snprintf(kind, sizeof kind, " (mixed round, k = %d)", rk);
+          else if (rk > -2) snprintf(kind, sizeof kind, rk == 0 ? " (wavefront round)" : " (row-local round)");
+          fprintf(stderr, "sco_sqp_solve: group %d round %d, %d problems active%s\n", g, r.retired, r.last_active, kind);
+        }
         if (r.last_active > 0) {
           if (r.issued + 1 < round_cap) { if ((rc = enqueue_round(g))) return rc; }
           else if (r.retired == r.issued) capped = true;
@@ -2143,7 +2207,7 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
     h->rounds = 1 + total_rounds;
     h->launches = 0;
     for (int g = 0; g < G; g++) h->launches += grp[g].retired;
-    h->wv_rounds = wv_rounds;
+    h->wv_rounds = wv_rounds; h->mixed_rounds = mixed_rounds; h->mixed_side = mixed_side;
   }
   if (capped) {
     // the launch cap ended the loop with problems still running (it is sized so that this cannot happen while every
@@ -2254,6 +2318,11 @@ extern "C" int sco_sqp_last_rounds(const sco_sqp *h, int *rounds) {
 }
 
 extern "C" int sco_debug_sqp_wv_rounds(const sco_sqp *h) { return h ? h->wv_rounds : -1; }
+extern "C" int sco_debug_sqp_mixed(const sco_sqp *h, int out[2]) {
+  if (!h || !out) return SCO_ERR_ARG;
+  out[0] = h->mixed_rounds; out[1] = h->mixed_side;
+  return SCO_OK;
+}
 extern "C" int sco_sqp_last_tiers(const sco_sqp *h, double ms[2], long long iters[2], int launches[2]) {
   if (!h || !ms || !iters || !launches) return SCO_ERR_ARG;
   SCO_ON_DEVICE(h->device);
@@ -2261,7 +2330,7 @@ extern "C" int sco_sqp_last_tiers(const sco_sqp *h, double ms[2], long long iter
   if (sco_qp_wv_iters(h->qp1, &wv_it)) return SCO_ERR_DEVICE;
   ms[0] = h->wv_ms; ms[1] = h->last_ms[2] - h->wv_ms;
   iters[0] = (long long)wv_it; iters[1] = -1;          // the other kernels': total (sco_sqp_fetch: admm_iters) minus these
-  launches[0] = h->wv_rounds; launches[1] = h->launches - h->wv_rounds;
+  launches[0] = h->wv_rounds; launches[1] = h->launches - h->wv_rounds + h->mixed_rounds;    // (a mixed round launches on both)
   return SCO_OK;
 }
 extern "C" int sco_sqp_last_launches(const sco_sqp *h, int *launches, int *groups) {
