@@ -431,6 +431,20 @@ int sco_sqp_last_tiers(const sco_sqp *h, double ms[2], long long iters[2], int l
 int sco_debug_sqp_mixed(const sco_sqp *h, int out[2]);
 int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu);
 
+/* The schedule of the SQP round loop on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/sqp_sched.h).  The
+ * SCO_SQP_* environment variables are read as by sco_sqp_solve.
+ * sco_debug_sqp_schedule: in = {batch, cus, admm_slice, adaptive_rho, max_iter, adaptive rho interval, max_qp_solves,
+ * problems alive after the projection round, the QP tier takes launch windows (0 / 1), the handle holds the wavefront tier
+ * (0 / 1), fewest live problems of a wavefront round, XCDs}; plan = {slice, groups, selection, has_wv, mix_on, mix_slack,
+ * mix_slices, mix_tail, depth, round_cap (saturated), xcds, trace level, then (b0, nb) of four groups}.  round_in (may be
+ * null) = {problems of the group, live problems, round index}; round_out = {wv_round, pass, nwg, mix_k, offset of the side
+ * window, QP tier (0 the launch decides, 1 row-local, 2 wavefront, 3 mixed), window passed, counts as a wavefront round}.
+ * sco_debug_stage_sweep: n intervals [begin_ms, end_ms) of stage 0 convexify, 1 QP setup, 2 ADMM, 3 decisions on one time
+ * axis; every instant is charged to the open stage of highest priority (ADMM > setup > convexify > decisions): ms[0 .. 3],
+ * ms[4] = the length of the union. */
+int sco_debug_sqp_schedule(const int in[12], int plan[20], const int round_in[3], int round_out[8]);
+int sco_debug_stage_sweep(int n, const double *begin_ms, const double *end_ms, const int *stage, double ms[5]);
+
 /* Per-problem decision trace of the last solve, for stage-wise parity checks:
  * trace[batch][cap][8] = {kind, merit, model_merit, new_merit, trust, penalty,
  * qp_status, qp_iters}; n_entries[batch].  kind: 0 projection QP, 1 accepted step,

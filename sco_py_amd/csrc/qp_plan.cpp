@@ -204,17 +204,3 @@ int qp_plan_build(int n, int m, const int *Pp, const int *Pi, const int *Ap, con
   }
   return 0;
 }
-
-int qp_mix_split(int live, int cus, int xcds, int slack, int per_cu) {
-  if (live <= 0 || cus <= 0 || xcds <= 0 || per_cu <= 0 || slack < 0 || cus % xcds) return 0;
-  if (live > per_cu * (cus - 1)) return 0;
-  const int room = cus / xcds;
-  auto up = [](int a, int b) { return (a + b - 1) / b; };
-  // (the left side is not monotone in k: it steps up every xcds problems and down every per_cu * xcds)
-  for (int k = live < cus ? live : cus; k > 0; k--)
-    if (up(k, xcds) + slack + up(up(live - k, xcds), per_cu) <= room) return k;
-  return 0;
-}
-extern "C" int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu) {
-  return qp_mix_split(live, cus, xcds, slack, per_cu);
-}

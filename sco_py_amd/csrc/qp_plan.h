@@ -51,11 +51,3 @@ struct QpPlan {
 // allow_elim = 2 eliminates only variables that sit in at most two rows.
 int qp_plan_build(int n, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
                   int allow_elim, QpPlan &out);
-
-// Mixed ADMM rounds of the SQP loop (sco_sqp_solve): how many of `live` problems leave the wavefront launch (per_cu
-// problems on a CU) for the row-local kernel (one problem on a whole CU) so that both launches are resident at once.
-// Workgroups are dealt to the XCDs in rotation and an XCD that receives one wavefront more than its free CUs hold would
-// double the round, so the count is taken per XCD: the largest k with
-//     ceil(k / xcds) + slack + ceil(ceil((live - k) / xcds) / per_cu) <= cus / xcds
-// and 0 when there is none, or while the wavefront launch alone still needs every CU (live > per_cu (cus - 1)).
-int qp_mix_split(int live, int cus, int xcds, int slack, int per_cu);

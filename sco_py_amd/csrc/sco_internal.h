@@ -27,6 +27,8 @@ int sco_hip_fail(hipError_t e, const char *what);
     if (_e != hipSuccess) return sco_hip_fail(_e, #call);                     \
   } while (0)
 
+#define SCO_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)     // pass an SCO_ERR_* on to the caller
+
 // Every ABI entry point runs on its handle's device and puts the caller's current device back on return
 // (a process that shares HIP with PyTorch or another library on a different device must not find its
 // current device changed by a call into this one).
@@ -253,7 +255,6 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
 // `grp` (may be null): run only problems [b0, b0 + nb) and on grp->stream instead of the handle's own (stream groups of
 // the SQP loop; row-local tier with the Gauss-Jordan inversion only, see sco_qp_supports_groups)
 // tier: 0 = the handle decides (wavefront tier when the batch has at least SCO_WV_MIN_PER_CU problems per CU), 1 = row-local
-// kernel, 2 = wavefront tier (handles that hold it; others ignore the field)
 // kernel, 2 = wavefront tier (handles that hold it; others ignore the field), 3 = MIXED round (handles with the wavefront tier
 // and an index list): the problems list[side_b0 .. side_b0 + side_nb) run on the row-local kernel for side_slices slices on
 // side_stream, the rest of the window -- [b0, side_b0) and [side_b0 + side_nb, b0 + nb), one of them empty -- on the wavefront
@@ -269,7 +270,7 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
 bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st);
 int sco_qp_adaptive_interval(const sco_qp_settings *st);
 int sco_wv_min_live(int cus, bool adaptive = false);      // fewest live problems for which a round runs on the wavefront tier
-bool sco_qp_has_wv(const sco_qp *qp, const sco_qp_settings *st);
+bool sco_qp_has_wv(const sco_qp *qp);
 int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out);      // iterations run by the wavefront kernel since the reset
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st);   // the handle holds the wavefront tier and these settings can use it
 bool sco_qp_can_adapt(const sco_qp *qp);   // false: this handle sits on the dense global-memory tier, which cannot park a solve

@@ -965,7 +965,7 @@ int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
   return SCO_OK;
 }
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st) { if (qp->use_wv) (void)hipMemsetAsync(qp->wvd.it_count, 0, sizeof(unsigned long long), st); }
-bool sco_qp_has_wv(const sco_qp *qp, const sco_qp_settings *st) { (void)st; return qp->use_wv; }
+bool sco_qp_has_wv(const sco_qp *qp) { return qp->use_wv; }
 bool sco_qp_can_adapt(const sco_qp *qp) { return !(qp->use_big && !qp->use_bt); }
 
 // Launch windows and index lists (QpGroup) exist for the paths the bench workloads take: row-local ADMM kernel with

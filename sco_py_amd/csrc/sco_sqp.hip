@@ -26,6 +26,7 @@
 // no inter-workgroup communication.  The host only reads one "active problems"
 // counter per round.
 #include "sco_admm_check.h"
+#include "sqp_sched.h"
 
 #include <algorithm>
 
@@ -50,9 +51,20 @@ struct SqpScalars {
   int flags;      // SCO_SQP_FLAG_*
 };
 
-#define SQP_MAX_GROUPS 4
-#define SQP_DEPTH 2        // rounds kept in flight per stream group
-#define SQP_MIX_DEFAULT 1  // mixed ADMM rounds (SCO_SQP_MIX): on
+// Events of a handle: created on demand behind a cursor, handed out in the same order by every solve, destroyed with the
+// handle.
+struct EventPool {
+  std::vector<hipEvent_t> ev;
+  size_t cur = 0;
+  unsigned flags = hipEventDefault;
+  int next(hipEvent_t *out) {
+    if (cur == ev.size()) { hipEvent_t e; SCO_HIP(hipEventCreateWithFlags(&e, flags)); ev.push_back(e); }
+    *out = ev[cur++];
+    return SCO_OK;
+  }
+  void rewind() { cur = 0; }
+  void destroy() { for (auto e : ev) (void)hipEventDestroy(e); ev.clear(); cur = 0; }
+};
 
 struct SqpDev {
   int b0;            // launch window of a stream group: workgroup g of the round kernels works on problem b0 + g
@@ -134,12 +146,14 @@ struct sco_sqp {
   hipStream_t stream = nullptr;
   // stream groups of the round loop (sco_sqp_solve): group 0 runs on `stream`, group g > 0 on gstream[g - 1]
   hipStream_t gstream[SQP_MAX_GROUPS - 1] = {};
-  std::vector<hipEvent_t> gevents[SQP_MAX_GROUPS], done;
+  EventPool events, gevents[SQP_MAX_GROUPS];          // stage marks of the main stream and of every group's rounds (timed)
+  EventPool done{{}, 0, hipEventDisableTiming};       // per (group, slot): the round's read-back has landed
+  EventPool mix_events{{}, 0, hipEventDisableTiming}; // three per mixed round (QpGroup::side_ev)
+  int xcds = 0;                      // sqp_xcds of the device, looked up by the first solve that needs it
   double *fetch_buf = nullptr;       // [2][B] merit and max violation of sco_sqp_fetch
   int *host_active = nullptr;        // pinned: [SQP_MAX_GROUPS][SQP_DEPTH] active counts read back per round
   int groups_used = 1;
   std::vector<void *> allocs;
-  std::vector<hipEvent_t> events;
   void *prog_buf[4] = {nullptr, nullptr, nullptr, nullptr};   // sco_sqp_load_program: words, row starts, constants, parameters
   void *objw_buf = nullptr;                                    // sco_sqp_load_obj_weights
   void *accw_buf = nullptr;                                    // sco_sqp_load_acc_weights
@@ -153,7 +167,6 @@ struct sco_sqp {
   int wv_rounds = 0;       // of them on the wavefront tier
   double wv_ms = 0.0;      // ADMM time of those rounds (part of last_ms[2])
   int mixed_rounds = 0, mixed_side = 0;   // of the wavefront rounds the mixed ones, and their side-window sizes summed
-  std::vector<hipEvent_t> mix_events;     // three per mixed round (QpGroup::side_ev), no timing
 };
 
 // --------------------------------------------------------------------------
@@ -1518,10 +1531,8 @@ extern "C" int sco_sqp_destroy(sco_sqp *h) {
   for (void *p : h->prog_buf) if (p) (void)hipFree(p);
   if (h->objw_buf) (void)hipFree(h->objw_buf);
   if (h->accw_buf) (void)hipFree(h->accw_buf);
-  for (auto e : h->events) (void)hipEventDestroy(e);
-  for (auto &ge : h->gevents) for (auto e : ge) (void)hipEventDestroy(e);
-  for (auto e : h->done) (void)hipEventDestroy(e);
-  for (auto e : h->mix_events) (void)hipEventDestroy(e);
+  h->events.destroy(); h->done.destroy(); h->mix_events.destroy();
+  for (auto &ge : h->gevents) ge.destroy();
   for (auto gs : h->gstream) if (gs) { (void)hipStreamSynchronize(gs); (void)hipStreamDestroy(gs); }
   if (h->host_active) (void)hipHostFree(h->host_active);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1817,13 +1828,6 @@ extern "C" int sco_sqp_fetch_stalled_groups(sco_sqp *h, unsigned int *stalled) {
   return SCO_OK;
 }
 
-static hipEvent_t next_event(sco_sqp *h, size_t &cursor) {
-  if (cursor == h->events.size()) {
-    hipEvent_t e; (void)hipEventCreate(&e); h->events.push_back(e);
-  }
-  return h->events[cursor++];
-}
-
 // Which problems take part in the next round.  A workgroup of the ADMM kernels fills a CU and the hardware deals the
 // workgroups of a launch to XCDs and shader engines in a fixed rotation, waiting for the engine whose turn it is: a
 // workgroup that finds its problem inactive and exits at once still takes its turn, so a launch of 1024 workgroups of
@@ -1842,6 +1846,7 @@ static hipEvent_t next_event(sco_sqp *h, size_t &cursor) {
 // index -- its head is the side window of the round.
 #define SEL_T 1024
 #define SEL_BUCKETS 1024
+static_assert(SEL_T == SQP_SEL_MAX && SCO_WV_PER_CU == SQP_WV_PER_CU, "sqp_sched.h plans with the kernels' sizes");
 // (r03: the kernel works on the problems [s.b0, s.b0 + nb) of a stream group and fills that group's part of the list, so
 // selection and stream groups combine: SCO_SQP_GROUPS)
 __global__ __launch_bounds__(SEL_T) void sqp_select_kernel(SqpDev s, QpDev q1, int cus, int slice, int max_iter, int cap, int nb, int order) {
@@ -1929,42 +1934,61 @@ __global__ void sqp_cap_kernel(SqpDev s) {
 }
 
 // XCDs the device deals the workgroups of a launch to (qp_mix_split).  HIP has no attribute for it: eight on the CDNA3 / CDNA4
-// parts whose CU count they divide, else one; SCO_SQP_XCDS overrides.
+// parts whose CU count they divide, else one (SCO_SQP_XCDS overrides: sqp_sched.cpp).
 static int sqp_xcds(int device, int cus) {
-  const char *e = getenv("SCO_SQP_XCDS");
-  if (e && atoi(e) > 0) return atoi(e);
   hipDeviceProp_t pr;
   if (hipGetDeviceProperties(&pr, device) != hipSuccess) { (void)hipGetLastError(); return 1; }
   const bool multi = !strncmp(pr.gcnArchName, "gfx94", 5) || !strncmp(pr.gcnArchName, "gfx95", 5);
   return (multi && cus > 0 && cus % 8 == 0) ? 8 : 1;
 }
 
-extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs) {
+// Timed events of one stream: event i ends the interval that is charged to stage[i] (0 convexify, 1 QP setup, 2 ADMM, 5 ADMM
+// on the wavefront tier, 3 decisions; < 0: nobody)
+struct StageMarks {
+  EventPool *pool = nullptr; hipStream_t st = nullptr;
+  std::vector<int> stage;
+  int take(int stg, hipEvent_t *e) { stage.push_back(stg); return pool->next(e); }      // an event the callee records
+  int mark(int stg) {
+    hipEvent_t e; SCO_TRY(take(stg, &e)); SCO_HIP(hipEventRecord(e, st));
+    return SCO_OK;
+  }
+};
+
+struct SqpGroupRun {                                   // one stream group of the round loop
+  int b0 = 0, nb = 0; hipStream_t st = nullptr;
+  int issued = 0, retired = 0, last_active = 1;        // rounds enqueued / read back; active count of the last one read
+  StageMarks marks;
+};
+struct SqpLoop {                                       // state of the round loop of one sco_sqp_solve
+  sco_sqp *h = nullptr;
+  SqpParamsDev p{};
+  sco_qp_settings qsl{};
+  SqpSchedule sc;
+  StageMarks main;                                     // the main stream: projection round, start of the stream groups
+  SqpGroupRun grp[SQP_MAX_GROUPS];
+  hipEvent_t done[SQP_MAX_GROUPS * SQP_DEPTH] = {};    // per (group, slot): the round's read-back has landed
+  int wv_rounds = 0, mixed_rounds = 0, mixed_side = 0;
+  std::vector<int> round_k;                            // per round of group 0: -1 row-local, 0 wavefront, k > 0 mixed (SCO_SQP_TRACE_ROUNDS)
+  bool capped = false;
+};
+
+static int sqp_check_state(const sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs) {
   if (!h || !params || !qs) { sco_set_error("sco_sqp_solve: null pointer"); return SCO_ERR_ARG; }
-  if (!h->loaded) { sco_set_error("sco_sqp_solve: call sco_sqp_load first"); return SCO_ERR_STATE; }
-  if ((h->desc.family & 15) == SCO_FAM_ARM_REACH && !h->target_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_target first"); return SCO_ERR_STATE;
-  }
-  if ((h->desc.family & SCO_FAM_FLAG_VEL_LIMITS) && !h->vel_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_vel_limit first"); return SCO_ERR_STATE;
-  }
-  if ((h->desc.family & SCO_FAM_FLAG_EE_COST) && !h->cost_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_ee_cost first"); return SCO_ERR_STATE;
-  }
-  if ((h->desc.family & SCO_FAM_FLAG_JOINT_LIMITS) && !h->jl_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_joint_limits first"); return SCO_ERR_STATE;
-  }
-  if (h->d.m_gen && !h->gen_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_linear_rows first"); return SCO_ERR_STATE;
-  }
-  if ((h->desc.family & 15) == SCO_FAM_STATE_PROGRAM && !h->prog_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_program first"); return SCO_ERR_STATE;
-  }
-  if ((h->desc.family & 15) == SCO_FAM_STATE_QUADRATIC && !h->quad_loaded) {
-    sco_set_error("sco_sqp_solve: call sco_sqp_load_quadratic first"); return SCO_ERR_STATE;
-  }
-  h->solved = false;            // a failed call must not leave an older result readable through fetch / trace
-  // settings are checked before the first launch: nothing on the device is touched by a call that is going to fail
+  const int fam = h->desc.family;
+  const char *missing = !h->loaded ? "sco_sqp_load"
+      : ((fam & 15) == SCO_FAM_ARM_REACH && !h->target_loaded) ? "sco_sqp_load_target"
+      : ((fam & SCO_FAM_FLAG_VEL_LIMITS) && !h->vel_loaded) ? "sco_sqp_load_vel_limit"
+      : ((fam & SCO_FAM_FLAG_EE_COST) && !h->cost_loaded) ? "sco_sqp_load_ee_cost"
+      : ((fam & SCO_FAM_FLAG_JOINT_LIMITS) && !h->jl_loaded) ? "sco_sqp_load_joint_limits"
+      : (h->d.m_gen && !h->gen_loaded) ? "sco_sqp_load_linear_rows"
+      : ((fam & 15) == SCO_FAM_STATE_PROGRAM && !h->prog_loaded) ? "sco_sqp_load_program"
+      : ((fam & 15) == SCO_FAM_STATE_QUADRATIC && !h->quad_loaded) ? "sco_sqp_load_quadratic" : nullptr;
+  if (missing) { sco_set_error(std::string("sco_sqp_solve: call ") + missing + " first"); return SCO_ERR_STATE; }
+  return SCO_OK;
+}
+
+// settings are checked before the first launch: nothing on the device is touched by a call that is going to fail
+static int sqp_check_settings(const sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs) {
   if (qs->max_iter <= 0 || !(qs->rho > 0) || !(qs->sigma > 0) || qs->scaling < 0 || !(qs->alpha > 0) || !(qs->alpha < 2)) {
     sco_set_error("sco_sqp_solve: bad QP settings (max_iter, rho, sigma > 0; 0 < alpha < 2; scaling >= 0)"); return SCO_ERR_ARG;
   }
@@ -1982,286 +2006,254 @@ extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco
       return SCO_ERR_CAPACITY;
     }
   }
-  SCO_ON_DEVICE(h->device);
-  SqpDev &s = h->d;
-  SqpParamsDev p{params->improve_ratio_threshold, params->min_trust_region_size, params->min_approx_improve,
-                 params->trust_shrink_ratio, params->trust_expand_ratio, params->cnt_tolerance,
-                 params->merit_coeff_increase_ratio, params->initial_trust_region_size, params->initial_penalty_coeff,
-                 params->max_merit_coeff_increases, params->compound_penalty, params->duplicate_rows,
-                 params->max_sqp_iters > 0 ? params->max_sqp_iters : 10000, params->memoize_rounded ? 1 : 0};
+  return SCO_OK;
+}
+
+// ---- round 0: projection onto the linear constraints, DEFAULT QP settings (Q7); *n_active: the problems that go on
+static int sqp_projection_round(sco_sqp *h, const SqpParamsDev &p, StageMarks &main, int *n_active) {
+  const SqpDev &s = h->d;
   const dim3 grid(s.batch), block(SCO_BLOCK);
-  size_t ec = 0;
-  std::vector<int> stage;   // stage id of the interval that ENDS at event i
-  auto mark = [&](int st) { hipEvent_t e = next_event(h, ec); (void)hipEventRecord(e, h->stream); stage.push_back(st); };
-  mark(-1);
-  // ---- round 0: projection onto the linear constraints, DEFAULT QP settings (Q7)
+  SCO_TRY(main.mark(-1));
   SCO_HIP(hipMemsetAsync(s.n_active, 0, sizeof(int), h->stream));
   hipLaunchKernelGGL(sqp_proj_assemble_kernel, grid, block, 0, h->stream, s, h->qp0->d);
   SCO_HIP(hipGetLastError());
-  mark(0);
+  SCO_TRY(main.mark(0));
   sco_qp_settings q0s; sco_qp_default_settings(&q0s);
-  hipEvent_t mid = next_event(h, ec); stage.push_back(1);
-  int rc = sco_qp_launch(h->qp0, &q0s, nullptr, mid);
-  if (rc) return rc;
-  mark(2);
+  hipEvent_t mid;
+  SCO_TRY(main.take(1, &mid));
+  SCO_TRY(sco_qp_launch(h->qp0, &q0s, nullptr, mid));
+  SCO_TRY(main.mark(2));
   hipLaunchKernelGGL(sqp_proj_post_kernel, grid, block, 0, h->stream, s, h->qp0->d, h->qp1->d, p);
   SCO_HIP(hipGetLastError());
-  mark(3);
-  int n_active = 0;
-  SCO_HIP(hipMemcpyAsync(&n_active, s.n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  SCO_TRY(main.mark(3));
+  SCO_HIP(hipMemcpyAsync(n_active, s.n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   SCO_HIP(hipStreamSynchronize(h->stream));
-  h->rounds = 1;
-  // ---- rounds: one QP solve per active problem
-  sco_qp_settings qsl = *qs;
+  return SCO_OK;
+}
+
+// the penalty QP's handle before the first round: settings of the rounds' QPs (*qsl), nothing parked, counters at zero
+static int sqp_reset_penalty_qp(sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs, sco_qp_settings *qsl) {
+  *qsl = *qs;
   if (params->warm_start_qps) {
     // beyond parity: every penalty QP starts from the previous one's solution; the first one from zero
-    qsl.warm_start = 1;
+    qsl->warm_start = 1;
     const QpDev &q1 = h->qp1->d;
     SCO_HIP(hipMemsetAsync(q1.x, 0, (size_t)q1.batch * q1.n * sizeof(double), h->stream));
     SCO_HIP(hipMemsetAsync(q1.y, 0, (size_t)q1.batch * q1.m * sizeof(double), h->stream));
     h->qp1->solved_once = true;
   }
-  // time slicing (scheduling only): every launch advances each active QP by at most `slice` ADMM iterations; a
-  // problem whose QP ended goes through post / pre / setup and joins the next launch with its next QP
-  // default slice: 6250 iterations (7-DOF x 20: 964 ms per 1024-batch step against 1106 unsliced); with adaptive rho
-  // the QPs are short and every rho change costs its problem a relaunch, so the slice is shorter (scripts/gpu_adaptive_slice_sweep.py)
-  int slice_req = params->admm_slice < 0 ? 0 : (params->admm_slice > 0 ? params->admm_slice : (qs->adaptive_rho ? 2000 : 6250));
-  if (params->admm_slice == 0) { const char *se = getenv("SCO_SQP_SLICE"); if (se && atoi(se) > 0) slice_req = atoi(se); }   // tuning aid: the default slice
-  if (params->admm_slice == 0) {
-    // with at most one problem per CU there is nobody to hand a CU to: slicing would only add relaunches
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && s.batch <= cus) slice_req = 0;
-  }
-  SCO_HIP(hipMemsetAsync(h->qp1->d.prog, 0, (size_t)s.batch * sizeof(int), h->stream));
+  SCO_HIP(hipMemsetAsync(h->qp1->d.prog, 0, (size_t)h->d.batch * sizeof(int), h->stream));
   sco_qp_wv_iters_reset(h->qp1, h->stream);
-  long long slices_per_qp = slice_req > 0 ? (qsl.max_iter + slice_req - 1) / slice_req : 1;
-  if (qsl.adaptive_rho) slices_per_qp += qsl.max_iter / sco_qp_adaptive_interval(&qsl) + 1;    // a launch per rho change at most
-  // (a round with selection runs at least half of the active problems, hence the factor 2)
-  const long long round_cap = 2 * ((long long)p.max_qp_solves + 8) * slices_per_qp;
-  // ---- scheduling of the rounds (results never depend on it).  A lock-step round costs ceil(active / CUs) passes of
-  // workgroups, so once problems start to finish the last pass of every round is partly empty
-  // (profiles/r02_launches.txt: 737 ms per step against 630 ms of work).  Default: ROUND SELECTION -- with more active
-  // problems than CUs a round runs a whole number of passes, the problems with most in front of them first
-  // (sqp_select_kernel), and SQP_DEPTH rounds are enqueued ahead so the device never waits for the host.
-  // Opt-in on top (SCO_SQP_GROUPS = 2..4): the batch is cut into contiguous STREAM GROUPS that run their rounds
-  // independently on streams of their own -- each with its own selection since r03 -- so that one group's launch fills the
-  // CUs the end of another's leaves free.  (Measured on the 1024-problem 7x20 step: DESIGN.md 3.3.)
-  int G = 1, cus = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  {
-    const char *ge = getenv("SCO_SQP_GROUPS");
-    const int want = ge ? atoi(ge) : 1;
-    if (slice_req > 0 && sco_qp_supports_groups(h->qp1, &qsl) && cus > 0 && s.batch >= 2 * cus)
-      G = std::max(1, std::min(std::min(want, SQP_MAX_GROUPS), s.batch / cus));
+  return SCO_OK;
+}
+
+static SqpSchedule sqp_plan(sco_sqp *h, int admm_slice, const sco_qp_settings &qsl, int max_qp_solves, int n_active) {
+  SqpSchedIn in;
+  in.batch = h->d.batch;
+  (void)hipDeviceGetAttribute(&in.cus, hipDeviceAttributeMultiprocessorCount, h->device);
+  in.admm_slice = admm_slice; in.max_qp_solves = max_qp_solves; in.n_active = n_active;
+  in.adaptive_rho = qsl.adaptive_rho; in.max_iter = qsl.max_iter;
+  in.adaptive_interval = qsl.adaptive_rho ? sco_qp_adaptive_interval(&qsl) : 0;
+  in.supports_groups = sco_qp_supports_groups(h->qp1, &qsl);
+  in.handle_wv = sco_qp_has_wv(h->qp1);
+  in.wv_min = sco_wv_min_live(in.cus, qsl.adaptive_rho != 0);
+  if (in.handle_wv) {                           // (mixed rounds need the wavefront tier; the device is asked once per handle)
+    if (!h->xcds) h->xcds = sqp_xcds(h->device, in.cus);
+    in.xcds = h->xcds;
   }
-  const char *sel_env = getenv("SCO_SQP_SELECT");
-  const bool select = slice_req > 0 && cus > 0 && s.batch > cus && sco_qp_supports_groups(h->qp1, &qsl) &&
-                      !(sel_env && sel_env[0] == '0');
-  if (getenv("SCO_SQP_TRACE_ROUNDS")) fprintf(stderr, "sco_sqp_solve: %d CUs, %d stream group(s), round selection %s, slice %d\n", cus, G, select ? "on" : "off", slice_req);
-  // Tier of a round (handles whose penalty QP has the wavefront tier; warm-started QPs as in parity mode, adaptive rho has
-  // no round selection and reaches the tier through wv_plain below): with at least wv_min live
-  // problems the round runs on the wavefront tier -- every live problem at once, four per CU -- below that on the row-local
-  // kernel, one problem per CU in whole passes.  The first is the higher THROUGHPUT while the batch is alive (1024 / 3.1 us
-  // against 256 / 0.95 us per iteration), the second the lower LATENCY for the tail of a step; a problem's QP changes kernel
-  // at a slice boundary (the parked state is common).  Both kernels agree to rounding (1e-14), not bit for bit: for batches
-  // that ever have wv_min live problems the last bits of a result depend on the schedule (SCO_WV_MIN_PER_CU=1e9: never).
-  const bool has_wv = select && sco_qp_has_wv(h->qp1, &qsl);
-  const int wv_min = sco_wv_min_live(cus, qsl.adaptive_rho != 0);
-  // MIXED rounds (SCO_SQP_MIX, one stream group, fixed rho): a wavefront round with fewer live problems than the chip holds
-  // leaves CUs empty.  The k problems with most in front of them -- the head of the round's list, which sqp_select_kernel then
-  // sorts -- run on the row-local kernel on those CUs instead, mix_slices slices in the time of one wavefront slice, beside the
-  // wavefront launch over the rest of the list (sco_qp_launch_sliced, tier 3; k: qp_mix_split).  Per problem the sequence of QPs
-  // and every decision is unchanged; which kernel runs a given slice moves, as at wv_min.  SCO_SQP_MIX_PICK=tail (test hook)
-  // takes the side window from the end of the list in odd rounds, so that problems change sides in both directions.
-  auto env_int = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-  const bool mix_on = has_wv && G == 1 && !qsl.adaptive_rho && env_int("SCO_SQP_MIX", SQP_MIX_DEFAULT) != 0;
-  const int mix_slack = std::max(0, env_int("SCO_SQP_MIX_SLACK", 1)), mix_slices = std::max(1, env_int("SCO_SQP_MIX_SLICES", 2));
-  const int xcds = mix_on ? sqp_xcds(h->device, cus) : 1;
-  bool mix_tail = false;
-  { const char *pe = getenv("SCO_SQP_MIX_PICK"); mix_tail = pe && !strcmp(pe, "tail"); }
-  if (mix_on && !h->gstream[0]) SCO_HIP(hipStreamCreate(&h->gstream[0]));
-  size_t mix_ec = 0;
-  int mixed_rounds = 0, mixed_side = 0;
-  std::vector<int> round_k;                     // per round of group 0: -1 row-local, 0 wavefront, k > 0 mixed (SCO_SQP_TRACE_ROUNDS)
-  h->groups_used = G;
-  for (int g = 1; g < G; g++)
+  in.env = sqp_sched_env();
+  return sqp_schedule_plan(in);
+}
+
+static int sqp_loop_start(SqpLoop &L) {
+  sco_sqp *h = L.h;
+  const SqpSchedule &sc = L.sc;
+  if (sc.trace) fprintf(stderr, "sco_sqp_solve: %d CUs, %d stream group(s), round selection %s, slice %d\n", sc.cus, sc.G, sc.select ? "on" : "off", sc.slice);
+  if (sc.mix_on && !h->gstream[0]) SCO_HIP(hipStreamCreate(&h->gstream[0]));
+  h->groups_used = sc.G;
+  for (int g = 1; g < sc.G; g++)
     if (!h->gstream[g - 1]) SCO_HIP(hipStreamCreate(&h->gstream[g - 1]));
-  struct Group {
-    int b0 = 0, nb = 0; hipStream_t st = nullptr;
-    int issued = 0, retired = 0, last_active = 1;      // rounds enqueued / read back; active count of the last one read
-    size_t ec = 0; std::vector<int> stage;              // event cursor and stage ids (as for the main stream)
-    double ms[5] = {0, 0, 0, 0, 0};
-  } grp[SQP_MAX_GROUPS];
-  for (int g = 0; g < G; g++) {
-    grp[g].b0 = (int)((long long)s.batch * g / G); grp[g].nb = (int)((long long)s.batch * (g + 1) / G) - grp[g].b0;
-    grp[g].st = g == 0 ? h->stream : h->gstream[g - 1];
-    grp[g].last_active = G == 1 ? n_active : grp[g].nb;       // upper bound of the group's live problems
+  for (int g = 0; g < sc.G; g++) {
+    SqpGroupRun &r = L.grp[g];
+    r.b0 = sc.grp[g].b0; r.nb = sc.grp[g].nb; r.last_active = sc.grp[g].live;
+    r.st = g == 0 ? h->stream : h->gstream[g - 1];
+    h->gevents[g].rewind();
+    r.marks.pool = &h->gevents[g]; r.marks.st = r.st;
   }
-  auto gevent = [&](int g) -> hipEvent_t {
-    Group &r = grp[g];
-    if (r.ec == h->gevents[g].size()) { hipEvent_t e; (void)hipEventCreate(&e); h->gevents[g].push_back(e); }
-    return h->gevents[g][r.ec++];
-  };
-  auto gmark = [&](int g, int st) { hipEvent_t e = gevent(g); (void)hipEventRecord(e, grp[g].st); grp[g].stage.push_back(st); };
-  std::vector<hipEvent_t> &done = h->done;          // per (group, slot): the round's read-back has landed
-  while (done.size() < (size_t)G * SQP_DEPTH) { hipEvent_t e; SCO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); done.push_back(e); }
-  int wv_rounds = 0;
-  auto enqueue_round = [&](int g) -> int {
-    Group &r = grp[g];
-    SqpDev sg = s; sg.b0 = r.b0; sg.n_active = s.n_active + g;
-    if (r.issued == 0) gmark(g, -1);
-    if (!select) SCO_HIP(hipMemsetAsync(sg.n_active, 0, sizeof(int), r.st));
-    sg.list = nullptr;
-    int nwg = r.nb;                              // workgroups of this round's kernels
-    const bool wv_round = has_wv && r.last_active >= wv_min;
-    int mix_k = 0;                               // side window of a mixed round
-    if (select) {
-      // compact launch: as many workgroups as the selection can let run, sized from the newest active count the host has
-      // (a pass of the chip = one problem per CU, four on the wavefront tier)
-      const int pass = wv_round ? 4 * cus : cus;
-      nwg = std::max(1, r.last_active <= pass ? r.last_active : (r.last_active / pass) * pass);
-      if (mix_on && wv_round && r.last_active < SCO_WV_PER_CU * cus && nwg <= SEL_T) {
-        mix_k = qp_mix_split(r.last_active, cus, xcds, mix_slack, SCO_WV_PER_CU);
-        if (mix_k >= nwg) mix_k = 0;
-      }
-      hipLaunchKernelGGL(sqp_select_kernel, dim3(1), dim3(SEL_T), 0, r.st, sg, h->qp1->d, pass, slice_req, qsl.max_iter, nwg, r.nb, mix_k > 0 ? 1 : 0);
-      SCO_HIP(hipGetLastError());
-      sg.list = s.list_buf;
-    }
-    if (h->desc.family & SCO_FAM_FLAG_OBJ_WIDE)   // the objective terms' sweep on one wavefront per term, matrices in LDS
-      hipLaunchKernelGGL(sqp_pre_wide_kernel, dim3(nwg), block, WIDE_LDS_BYTES, r.st, sg, h->qp1->d, p);
-    else
-      hipLaunchKernelGGL(sqp_pre_kernel, dim3(nwg), block, 0, r.st, sg, h->qp1->d, p);
-    SCO_HIP(hipGetLastError());
-    gmark(g, 0);
-    hipEvent_t gm = gevent(g); r.stage.push_back(1);
-    QpGroup win{r.b0, nwg, r.st, sg.list, has_wv ? (wv_round ? 2 : 1) : 0};
-    if (mix_k > 0) {
-      win.tier = 3; win.side_nb = mix_k; win.side_slices = mix_slices; win.side_stream = h->gstream[0];
-      win.side_b0 = r.b0 + ((mix_tail && (r.issued & 1)) ? nwg - mix_k : 0);
-      for (int e = 0; e < 3; e++) {
-        if (mix_ec == h->mix_events.size()) { hipEvent_t ev; SCO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); h->mix_events.push_back(ev); }
-        win.side_ev[e] = h->mix_events[mix_ec++];
-      }
-      mixed_rounds++; mixed_side += mix_k;
-    }
-    if (g == 0) round_k.push_back(mix_k > 0 ? mix_k : (wv_round ? 0 : -1));
-    // without round selection (at most one problem per CU) the launch itself goes by its size (sco_qp_launch_sliced): with
-    // SCO_WV_MIN_PER_CU lowered such a round runs on the wavefront tier too, and is counted as one
-    const bool wv_plain = !has_wv && sco_qp_has_wv(h->qp1, &qsl) && nwg >= wv_min;
-    if (wv_round || wv_plain) wv_rounds++;
-    const int rc_ = sco_qp_launch_sliced(h->qp1, &qsl, s.newqp, s.active, slice_req, gm, nullptr, (G > 1 || select) ? &win : nullptr);
-    if (rc_) return rc_;
-    gmark(g, (wv_round || wv_plain) ? 5 : 2);
-    hipLaunchKernelGGL(sqp_post_kernel, dim3(nwg), block, 0, r.st, sg, h->qp1->d, p);
-    SCO_HIP(hipGetLastError());
-    gmark(g, 3);
-    const int slot = r.issued % SQP_DEPTH;
-    SCO_HIP(hipMemcpyAsync(h->host_active + g * SQP_DEPTH + slot, sg.n_active, sizeof(int), hipMemcpyDeviceToHost, r.st));
-    SCO_HIP(hipEventRecord(done[(size_t)g * SQP_DEPTH + slot], r.st));
-    r.issued++;
-    return SCO_OK;
-  };
-  // Rounds kept enqueued ahead of the host: SQP_DEPTH where a round's read-back would otherwise leave the device idle
-  // (selection, stream groups, time slices); ONE for the plain unsliced loop over a batch that fits the CUs (the B = 1
-  // latency case): there a second round in flight would only be a trailing all-inactive launch sequence per solve.
-  const int depth = (!select && G == 1 && slice_req == 0) ? 1 : SQP_DEPTH;
-  bool capped = false;
-  if (G > 1) {
+  h->done.rewind(); h->mix_events.rewind();
+  for (int i = 0; i < sc.G * SQP_DEPTH; i++)
+    SCO_TRY(h->done.next(&L.done[i]));
+  if (sc.G > 1) {
     // the other groups' streams start behind the memsets queued on the main stream above (prog reset, warm-start zeroing)
-    hipEvent_t ready = next_event(h, ec); stage.push_back(-2);
+    hipEvent_t ready;
+    SCO_TRY(L.main.take(-2, &ready));
     SCO_HIP(hipEventRecord(ready, h->stream));
-    for (int g = 1; g < G; g++) SCO_HIP(hipStreamWaitEvent(grp[g].st, ready, 0));
+    for (int g = 1; g < sc.G; g++) SCO_HIP(hipStreamWaitEvent(L.grp[g].st, ready, 0));
   }
-  if (n_active > 0) {
-    for (int k = 0; k < depth; k++)
-      for (int g = 0; g < G; g++)
-        if ((rc = enqueue_round(g))) return rc;
-    for (bool busy = true; busy;) {
-      busy = false;
-      for (int g = 0; g < G; g++) {
-        Group &r = grp[g];
-        if (r.retired == r.issued) continue;
-        busy = true;
-        const int slot = r.retired % SQP_DEPTH;
-        SCO_HIP(hipEventSynchronize(done[(size_t)g * SQP_DEPTH + slot]));
-        r.last_active = h->host_active[g * SQP_DEPTH + slot];
-        r.retired++;
-        if (getenv("SCO_SQP_TRACE_ROUNDS") && (r.retired < 40 || r.retired % 100 == 0 || atoi(getenv("SCO_SQP_TRACE_ROUNDS")) >= 2)) {   // (2: every round)
-          const int rk = (g == 0 && has_wv) ? round_k[r.retired - 1] : -2;
-          char kind[48] = "";
-          if (rk > 0) snprintf(kind, sizeof kind, " (mixed round, k = %d)", rk);
-          else if (rk > -2) snprintf(kind, sizeof kind, rk == 0 ? " (wavefront round)" : " (row-local round)");
-          fprintf(stderr, "sco_sqp_solve: group %d round %d, %d problems active%s\n", g, r.retired, r.last_active, kind);
-        }
-        if (r.last_active > 0) {
-          if (r.issued + 1 < round_cap) { if ((rc = enqueue_round(g))) return rc; }
-          else if (r.retired == r.issued) capped = true;
-        }
+  return SCO_OK;
+}
+
+// one round of stream group g: [selection ->] pre -> QP setup + ADMM slice -> post -> read-back of the active count
+static int sqp_enqueue_round(SqpLoop &L, int g) {
+  sco_sqp *h = L.h;
+  const SqpSchedule &sc = L.sc;
+  const SqpDev &s = h->d;
+  SqpGroupRun &r = L.grp[g];
+  const SqpRound rp = sqp_round_plan(sc, r.nb, r.last_active, r.issued);
+  const dim3 block(SCO_BLOCK);
+  SqpDev sg = s; sg.b0 = r.b0; sg.n_active = s.n_active + g;
+  if (r.issued == 0) SCO_TRY(r.marks.mark(-1));
+  if (!sc.select) SCO_HIP(hipMemsetAsync(sg.n_active, 0, sizeof(int), r.st));
+  sg.list = nullptr;
+  if (sc.select) {
+    hipLaunchKernelGGL(sqp_select_kernel, dim3(1), dim3(SEL_T), 0, r.st, sg, h->qp1->d, rp.pass, sc.slice, L.qsl.max_iter, rp.nwg, r.nb, rp.mix_k > 0 ? 1 : 0);
+    SCO_HIP(hipGetLastError());
+    sg.list = s.list_buf;
+  }
+  if (h->desc.family & SCO_FAM_FLAG_OBJ_WIDE)   // the objective terms' sweep on one wavefront per term, matrices in LDS
+    hipLaunchKernelGGL(sqp_pre_wide_kernel, dim3(rp.nwg), block, WIDE_LDS_BYTES, r.st, sg, h->qp1->d, L.p);
+  else
+    hipLaunchKernelGGL(sqp_pre_kernel, dim3(rp.nwg), block, 0, r.st, sg, h->qp1->d, L.p);
+  SCO_HIP(hipGetLastError());
+  SCO_TRY(r.marks.mark(0));
+  hipEvent_t gm;
+  SCO_TRY(r.marks.take(1, &gm));
+  QpGroup win{r.b0, rp.nwg, r.st, sg.list, rp.tier};
+  if (rp.mix_k > 0) {
+    win.side_nb = rp.mix_k; win.side_slices = sc.mix_slices; win.side_stream = h->gstream[0];
+    win.side_b0 = r.b0 + rp.side_off;
+    for (int e = 0; e < 3; e++)
+      SCO_TRY(h->mix_events.next(&win.side_ev[e]));
+    L.mixed_rounds++; L.mixed_side += rp.mix_k;
+  }
+  if (g == 0) L.round_k.push_back(rp.mix_k > 0 ? rp.mix_k : (rp.wv_round ? 0 : -1));
+  if (rp.counts_as_wv) L.wv_rounds++;
+  SCO_TRY(sco_qp_launch_sliced(h->qp1, &L.qsl, s.newqp, s.active, sc.slice, gm, nullptr, rp.window ? &win : nullptr));
+  SCO_TRY(r.marks.mark(rp.counts_as_wv ? 5 : 2));
+  hipLaunchKernelGGL(sqp_post_kernel, dim3(rp.nwg), block, 0, r.st, sg, h->qp1->d, L.p);
+  SCO_HIP(hipGetLastError());
+  SCO_TRY(r.marks.mark(3));
+  const int slot = r.issued % SQP_DEPTH;
+  SCO_HIP(hipMemcpyAsync(h->host_active + g * SQP_DEPTH + slot, sg.n_active, sizeof(int), hipMemcpyDeviceToHost, r.st));
+  SCO_HIP(hipEventRecord(L.done[g * SQP_DEPTH + slot], r.st));
+  r.issued++;
+  return SCO_OK;
+}
+
+// SCO_SQP_TRACE_ROUNDS: the first 40 rounds of a group and every 100th (2: every round)
+static void sqp_trace_round(const SqpLoop &L, int g) {
+  const SqpGroupRun &r = L.grp[g];
+  if (!L.sc.trace || !(r.retired < 40 || r.retired % 100 == 0 || L.sc.trace >= 2)) return;
+  const int rk = (g == 0 && L.sc.has_wv) ? L.round_k[r.retired - 1] : -2;
+  char kind[48] = "";
+  if (rk > 0) snprintf(kind, sizeof kind, " (mixed round, k = %d)", rk);
+  else if (rk > -2) snprintf(kind, sizeof kind, rk == 0 ? " (wavefront round)" : " (row-local round)");
+  fprintf(stderr, "sco_sqp_solve: group %d round %d, %d problems active%s\n", g, r.retired, r.last_active, kind);
+}
+
+// ---- rounds: one QP solve (or one slice of it) per active problem, sc.depth rounds of every group enqueued ahead
+static int sqp_run_rounds(SqpLoop &L) {
+  const SqpSchedule &sc = L.sc;
+  for (int k = 0; k < sc.depth; k++)
+    for (int g = 0; g < sc.G; g++)
+      SCO_TRY(sqp_enqueue_round(L, g));
+  for (bool busy = true; busy;) {
+    busy = false;
+    for (int g = 0; g < sc.G; g++) {
+      SqpGroupRun &r = L.grp[g];
+      if (r.retired == r.issued) continue;
+      busy = true;
+      const int slot = r.retired % SQP_DEPTH;
+      SCO_HIP(hipEventSynchronize(L.done[g * SQP_DEPTH + slot]));
+      r.last_active = L.h->host_active[g * SQP_DEPTH + slot];
+      r.retired++;
+      sqp_trace_round(L, g);
+      if (r.last_active > 0) {
+        if (r.issued + 1 < sc.round_cap) SCO_TRY(sqp_enqueue_round(L, g));
+        else if (r.retired == r.issued) L.capped = true;
       }
     }
   }
-  {
-    int total_rounds = 0;
-    for (int g = 0; g < G; g++) total_rounds = std::max(total_rounds, grp[g].retired);
-    h->rounds = 1 + total_rounds;
-    h->launches = 0;
-    for (int g = 0; g < G; g++) h->launches += grp[g].retired;
-    h->wv_rounds = wv_rounds; h->mixed_rounds = mixed_rounds; h->mixed_side = mixed_side;
-  }
-  if (capped) {
+  return SCO_OK;
+}
+
+// the counters the ABI reports; problems the launch cap left running are marked
+static int sqp_store_counters(SqpLoop &L) {
+  sco_sqp *h = L.h;
+  int total_rounds = 0;
+  h->launches = 0;
+  for (int g = 0; g < L.sc.G; g++) { total_rounds = std::max(total_rounds, L.grp[g].retired); h->launches += L.grp[g].retired; }
+  h->rounds = 1 + total_rounds;
+  h->wv_rounds = L.wv_rounds; h->mixed_rounds = L.mixed_rounds; h->mixed_side = L.mixed_side;
+  if (L.capped) {
     // the launch cap ended the loop with problems still running (it is sized so that this cannot happen while every
     // problem respects max_sqp_iters): they are reported as capped failures, never silently as finished
-    hipLaunchKernelGGL(sqp_cap_kernel, dim3((s.batch + SCO_BLOCK - 1) / SCO_BLOCK), block, 0, h->stream, s);
+    hipLaunchKernelGGL(sqp_cap_kernel, dim3((h->d.batch + SCO_BLOCK - 1) / SCO_BLOCK), dim3(SCO_BLOCK), 0, h->stream, h->d);
     SCO_HIP(hipGetLastError());
     SCO_HIP(hipStreamSynchronize(h->stream));
   }
-  // ---- timing: sum the event intervals by stage.  The rounds of different stream groups overlap, so their intervals
-  // are laid on one time axis (milliseconds after the first event of the call) and every instant is charged to ONE
-  // stage: the ADMM launch if any group is inside one, else QP setup, else convexify, else the decisions -- the ADMM
-  // figure is then the wall time during which at least one ADMM launch was resident or queued behind another group's,
-  // and the stages add up to the wall time of the call.
+  return SCO_OK;
+}
+
+// ---- timing: sum the event intervals by stage.  With one stream group the intervals follow each other; the rounds of
+// several groups overlap and go through sqp_stage_sweep (every instant charged to one stage, so that the stages add up
+// to the wall time of the call).
+static void sqp_stage_times(SqpLoop &L) {
+  sco_sqp *h = L.h;
   double ms[5] = {0, 0, 0, 0, 0}, wv_ms = 0.0;
-  for (size_t i = 1; i < ec; i++) {
-    float t = 0; (void)hipEventElapsedTime(&t, h->events[i - 1], h->events[i]);
-    if (stage[i] >= 0) ms[stage[i]] += t;
-    ms[4] += t;
-  }
-  if (G == 1) {
-    Group &r = grp[0];
-    for (size_t i = 1; i < r.ec; i++) {
-      float t = 0; (void)hipEventElapsedTime(&t, h->gevents[0][i - 1], h->gevents[0][i]);
-      if (r.stage[i] == 5) { ms[2] += t; wv_ms += t; }
-      else if (r.stage[i] >= 0) ms[r.stage[i]] += t;
+  // an ADMM launch on the wavefront tier (stage 5) is ADMM time, summed on the side as well (sco_sqp_last_tiers)
+  auto admm_stage = [&wv_ms](int stg, double dt) { if (stg != 5) return stg; wv_ms += dt; return 2; };
+  auto sum_consecutive = [&](const StageMarks &mk) {
+    for (size_t i = 1; i < mk.pool->cur; i++) {
+      float t = 0; (void)hipEventElapsedTime(&t, mk.pool->ev[i - 1], mk.pool->ev[i]);
+      const int stg = admm_stage(mk.stage[i], t);
+      if (stg >= 0) ms[stg] += t;
       ms[4] += t;
     }
-  } else {
-    struct Edge { double t; int stage, d; };
-    std::vector<Edge> edges;
-    for (int g = 0; g < G; g++) {
-      Group &r = grp[g];
+  };
+  sum_consecutive(L.main);
+  if (L.sc.G == 1) sum_consecutive(L.grp[0].marks);
+  else {
+    // milliseconds after the first event of the call
+    std::vector<double> t0, t1; std::vector<int> stg;
+    for (int g = 0; g < L.sc.G; g++) {
+      const std::vector<int> &stage = L.grp[g].marks.stage;
       double prev = 0.0;
-      for (size_t i = 0; i < r.ec; i++) {
-        float t = 0; (void)hipEventElapsedTime(&t, h->events[0], h->gevents[g][i]);
-        const int stg = r.stage[i] == 5 ? 2 : r.stage[i];
-        if (i > 0 && r.stage[i] == 5) wv_ms += t - prev;
-        if (i > 0 && stg >= 0 && t > prev) { edges.push_back({prev, stg, 1}); edges.push_back({(double)t, stg, -1}); }
+      for (size_t i = 0; i < h->gevents[g].cur; i++) {
+        float t = 0; (void)hipEventElapsedTime(&t, h->events.ev[0], h->gevents[g].ev[i]);
+        if (i > 0) { t0.push_back(prev); t1.push_back(t); stg.push_back(admm_stage(stage[i], t - prev)); }
         prev = t;
       }
     }
-    std::sort(edges.begin(), edges.end(), [](const Edge &x, const Edge &y) { return x.t < y.t; });
-    int open_[4] = {0, 0, 0, 0};
-    const int prio[4] = {2, 1, 0, 3};
-    for (size_t i = 0; i + 1 <= edges.size(); i++) {
-      if (i > 0) {
-        const double dt = edges[i].t - edges[i - 1].t;
-        for (int k : prio) if (open_[k] > 0) { ms[k] += dt; ms[4] += dt; break; }
-      }
-      open_[edges[i].stage] += edges[i].d;
-    }
+    sqp_stage_sweep(t0.data(), t1.data(), stg.data(), (int)stg.size(), ms);
   }
   memcpy(h->last_ms, ms, sizeof ms);
   h->wv_ms = wv_ms;
+}
+
+extern "C" int sco_sqp_solve(sco_sqp *h, const sco_sqp_params *params, const sco_qp_settings *qs) {
+  SCO_TRY(sqp_check_state(h, params, qs));
+  h->solved = false;            // a failed call must not leave an older result readable through fetch / trace
+  SCO_TRY(sqp_check_settings(h, params, qs));
+  SCO_ON_DEVICE(h->device);
+  SqpLoop L;
+  L.h = h;
+  L.p = SqpParamsDev{params->improve_ratio_threshold, params->min_trust_region_size, params->min_approx_improve,
+                     params->trust_shrink_ratio, params->trust_expand_ratio, params->cnt_tolerance,
+                     params->merit_coeff_increase_ratio, params->initial_trust_region_size, params->initial_penalty_coeff,
+                     params->max_merit_coeff_increases, params->compound_penalty, params->duplicate_rows,
+                     params->max_sqp_iters > 0 ? params->max_sqp_iters : 10000, params->memoize_rounded ? 1 : 0};
+  h->events.rewind();
+  L.main.pool = &h->events; L.main.st = h->stream;
+  int n_active = 0;
+  SCO_TRY(sqp_projection_round(h, L.p, L.main, &n_active));
+  h->rounds = 1;
+  SCO_TRY(sqp_reset_penalty_qp(h, params, qs, &L.qsl));
+  L.sc = sqp_plan(h, params->admm_slice, L.qsl, L.p.max_qp_solves, n_active);
+  SCO_TRY(sqp_loop_start(L));
+  if (n_active > 0) SCO_TRY(sqp_run_rounds(L));
+  SCO_TRY(sqp_store_counters(L));
+  sqp_stage_times(L);
   h->solved = true;
   return SCO_OK;
 }

@@ -1,4 +1,4 @@
-"""Side-window size of a mixed ADMM round (csrc/qp_plan.cpp: qp_mix_split, through sco_debug_mix_split): host arithmetic only.
+"""Side-window size of a mixed ADMM round (csrc/sqp_sched.cpp: qp_mix_split, through sco_debug_mix_split): host arithmetic only.
 
 A mixed round runs k of the live problems on the row-local kernel (one per CU) beside the wavefront launch over the rest
 (four per CU).  Workgroups are dealt to the XCDs in rotation, so the room is counted per XCD."""
