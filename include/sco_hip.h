@@ -445,6 +445,26 @@ int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu);
 int sco_debug_sqp_schedule(const int in[12], int plan[20], const int round_in[3], int round_out[8]);
 int sco_debug_stage_sweep(int n, const double *begin_ms, const double *end_ms, const int *stage, double ms[5]);
 
+/* What a launch on a QP handle does, on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/qp_tier.h).
+ * sco_debug_qp_launch_plan: in[24] = {on-chip kernel of the handle (0 row-local, 1 register-offset, 2 sliced-ELL, 3 generic),
+ * global-memory tier, its structured form, wavefront tier, Cholesky cross-check (0 / 1 each), batch, order of the core, CUs,
+ * adaptive_rho, adaptive_rho_interval, check_termination, max_iter, slice asked for, setup mask (0 an array, 1 all, 2 none),
+ * fewest problems of a wavefront launch (< 0: from the CUs and SCO_WV_MIN_PER_CU, as a launch does), then the launch window:
+ * given (0 / 1), b0, nb, tier, index list given, side_b0, side_nb, side_slices, side stream and its three events given};
+ * tol = adaptive_rho_tolerance.  out[15] = {return code, error (0 none, 1 window, 2 adaptive rho on the dense global-memory
+ * form, 3 adaptive settings, 4 mixed round), rounded slice (-1: the launch failed before it wrote one), workgroups, rho-init
+ * kernel runs, route (0 dense global memory, 1 structured, 2 on-chip), wavefront launch, mixed round, extra dense inverses
+ * (0 none, 1 for the window, 2 for the side window of a mixed round), Cholesky, tiles per thread of the sweep kernel, ADMM
+ * sequence (0 generic, 1 sliced-ELL, 2 register-offset, 3 row-local, 4 wavefront then row-local, 5 mixed), rho-estimate
+ * interval of the launch, fewest problems of a wavefront launch for these CUs and this rho mode, rho-estimate interval of
+ * these settings}.
+ * sco_debug_plan_tiers: the tiers a handle created now from the pattern last given to sco_debug_plan_build would run, under
+ * the SCO_QP_* switches as they stand: bit 0 row-local, 1 register-offset, 2 sliced-ELL kernel (at most one of the three;
+ * none: the generic kernel), 3 global-memory tier, 4 its structured form, 5 wavefront tier beside the row-local kernel,
+ * 6 block normal matrices on the matrix cores. */
+int sco_debug_qp_launch_plan(const int *in, const double *tol, int *out);
+int sco_debug_plan_tiers(int *mask);
+
 /* Per-problem decision trace of the last solve, for stage-wise parity checks:
  * trace[batch][cap][8] = {kind, merit, model_merit, new_merit, trust, penalty,
  * qp_status, qp_iters}; n_entries[batch].  kind: 0 projection QP, 1 accepted step,

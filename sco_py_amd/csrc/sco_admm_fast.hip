@@ -422,24 +422,13 @@ __global__ __launch_bounds__(FT) void qp_admm_fast_kernel(AdmmArgs a, FastDev f)
 // --------------------------------------------------------------------------
 // host glue
 // --------------------------------------------------------------------------
-template <typename T>
-static int up(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  allocs.push_back(p);
-  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T *)p;
-  return SCO_OK;
-}
-
 static int up_sell(std::vector<void *> &allocs, const SellHost &h, SellDev &dv) {
   dv.total = h.total;
   int rc;
-  if ((rc = up(allocs, h.base, &dv.base))) return rc;
-  if ((rc = up(allocs, h.width, &dv.width))) return rc;
-  if ((rc = up(allocs, h.idx, &dv.idx))) return rc;
-  if ((rc = up(allocs, h.src, &dv.src))) return rc;
+  if ((rc = sco_upload(allocs, h.base, &dv.base))) return rc;
+  if ((rc = sco_upload(allocs, h.width, &dv.width))) return rc;
+  if ((rc = sco_upload(allocs, h.idx, &dv.idx))) return rc;
+  if ((rc = sco_upload(allocs, h.src, &dv.src))) return rc;
   return SCO_OK;
 }
 
@@ -454,16 +443,8 @@ int fast_upload(const FastHost &fh, std::vector<void *> &allocs, FastDev &fd) {
 
 template <int TR, int TC, int CW, int RW, int PA, int PE, int NQ>
 static int launch_one(const AdmmArgs &a, const FastDev &fd, size_t lds, hipStream_t st) {
-  // hipFuncSetAttribute applies to the current device only
   static bool attr_done[64] = {};
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  dev_ &= 63;
-  if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_fast_kernel<TR, TC, CW, RW, PA, PE, NQ>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done[dev_] = true;
-  }
+  SCO_LDS_ATTR((qp_admm_fast_kernel<TR, TC, CW, RW, PA, PE, NQ>), 160 * 1024, attr_done);
   hipLaunchKernelGGL((qp_admm_fast_kernel<TR, TC, CW, RW, PA, PE, NQ>), dim3(a.d.batch), dim3(FT), lds, st, a, fd);
   SCO_HIP(hipGetLastError());
   return SCO_OK;

@@ -36,6 +36,10 @@
 #define CAP_N 512
 #define CAP_M 1024
 #define CAP_NC 160
+// static LDS of qp_admm_reg_kernel: its seven __shared__ arrays (s_xt, s_tv, s_ge, s_xc, s_rv, s_scr, s_red)
+#define REG_STATIC_LDS (8 * (4 * CAP_N + 3 * CAP_M + 2 * CAP_NC + RWV * 8))
+static_assert(REG_STATIC_LDS == 44032, "static LDS of qp_admm_reg_kernel");
+size_t reg_static_lds() { return REG_STATIC_LDS; }
 
 // --------------------------------------------------------------------------
 // host: per-thread programs
@@ -58,7 +62,7 @@ bool reg_plan_build(const QpPlan &pl, int CW, int RW, int PX, RegHost &rh) {
     build_sell(pl.n_e, pl.e_ptr, pl.pair_core, ident, rh.Ce);
     // room for the unrolled reads that run past the last slice
     rh.lds_bytes = 8 * ((size_t)rh.Ac.total + rh.Ar.total + rh.Ca.total + rh.Ce.total + 64 * 16);
-    if (rh.lds_bytes + 44032 > 160 * 1024) return false;
+    if (rh.lds_bytes + REG_STATIC_LDS > 160 * 1024) return false;
   }
   rh.TR = std::max(1, (pl.n_c + RGI - 1) / RGI);
   rh.TC = 2 * rh.TR;
@@ -484,40 +488,21 @@ __global__ __launch_bounds__(RT) void qp_admm_reg_kernel(RegArgs a) {
 // --------------------------------------------------------------------------
 // host glue
 // --------------------------------------------------------------------------
-template <typename T>
-static int upv(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  allocs.push_back(p);
-  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T *)p;
-  return SCO_OK;
-}
-
 int reg_upload(const RegHost &rh, std::vector<void *> &allocs, RegDev &rd) {
   int rc;
-  if ((rc = upv(allocs, rh.off, &rd.off))) return rc;
-  if ((rc = upv(allocs, rh.role, &rd.role))) return rc;
-  if ((rc = upv(allocs, rh.Ac.src, &rd.srcAc))) return rc;
-  if ((rc = upv(allocs, rh.Ar.src, &rd.srcAr))) return rc;
-  if ((rc = upv(allocs, rh.Ca.src, &rd.srcCa))) return rc;
-  if ((rc = upv(allocs, rh.Ce.src, &rd.srcCe))) return rc;
+  if ((rc = sco_upload(allocs, rh.off, &rd.off))) return rc;
+  if ((rc = sco_upload(allocs, rh.role, &rd.role))) return rc;
+  if ((rc = sco_upload(allocs, rh.Ac.src, &rd.srcAc))) return rc;
+  if ((rc = sco_upload(allocs, rh.Ar.src, &rd.srcAr))) return rc;
+  if ((rc = sco_upload(allocs, rh.Ca.src, &rd.srcCa))) return rc;
+  if ((rc = sco_upload(allocs, rh.Ce.src, &rd.srcCe))) return rc;
   return SCO_OK;
 }
 
 template <int TR, int TC, int CW, int RW, int PX>
 static int reg_launch_one(const RegArgs &ra, int batch, size_t lds, hipStream_t st) {
-  // hipFuncSetAttribute applies to the current device only
   static bool attr_done[64] = {};
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  dev_ &= 63;
-  if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_reg_kernel<TR, TC, CW, RW, PX>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 44032));
-    attr_done[dev_] = true;
-  }
+  SCO_LDS_ATTR((qp_admm_reg_kernel<TR, TC, CW, RW, PX>), 160 * 1024 - REG_STATIC_LDS, attr_done);
   hipLaunchKernelGGL((qp_admm_reg_kernel<TR, TC, CW, RW, PX>), dim3(batch), dim3(RT), lds, st, ra);
   SCO_HIP(hipGetLastError());
   return SCO_OK;

@@ -807,6 +807,13 @@ __device__ __forceinline__ double rl_reduce_al(const double (&acc)[AL_TR]) {
 #define RL_WAVE_SYNC() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 
+// What sco_qp_info adds to the handle's dynamic part (RlHost::lds_bytes) for the static LDS of qp_admm_rl_kernel.  NOT the
+// kernel's static LDS of today: the figure is the one reported since the kernel was written and is kept as reported.  The
+// __shared__ arrays below take 36 480 bytes today (37 888 in the aligned form), which is what rl_plan_build budgets 40 KB
+// for.
+#define RL_REPORTED_STATIC_LDS 30208
+size_t rl_reported_static_lds() { return RL_REPORTED_STATIC_LDS; }
+
 // LAY: 0 = 16 column groups of the W tile (5 x 9 at 140 core variables), 1 = 8 column groups (3 x 18, cheaper reduction, six
 // of the eight wavefronts carry W), 2 = 8 column groups with the aligned closed assignment (one barrier per iteration)
 template <int TR, int TC, int CW, bool ADAPT, int NS = 2, int LAY = 0>
@@ -1408,42 +1415,23 @@ extern "C" int sco_debug_stamps(double *out) {      // diagnostic build only
   return hipMemcpy(out, sco_debug_stamp_ptr, 128 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
 }
 #endif
-template <typename T>
-static int upl(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  allocs.push_back(p);
-  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T *)p;
-  return SCO_OK;
-}
-
 int rl_upload(const RlHost &rh, std::vector<void *> &allocs, RlDev &rd) {
   int rc;
-  if ((rc = upl(allocs, rh.off, &rd.off))) return rc;
-  if ((rc = upl(allocs, rh.role, &rd.role))) return rc;
-  if ((rc = upl(allocs, rh.Ac.src, &rd.srcAc))) return rc;
+  if ((rc = sco_upload(allocs, rh.off, &rd.off))) return rc;
+  if ((rc = sco_upload(allocs, rh.role, &rd.role))) return rc;
+  if ((rc = sco_upload(allocs, rh.Ac.src, &rd.srcAc))) return rc;
   for (int q = 0; q < LNS_MAX; q++)
-    if ((rc = upl(allocs, rh.Ar[q].src, &rd.srcAr[q]))) return rc;
-  if ((rc = upl(allocs, rh.pc_ptr, &rd.pc_ptr))) return rc;
-  if ((rc = upl(allocs, rh.pc_pos, &rd.pc_pos))) return rc;
-  if ((rc = upl(allocs, rh.pc_core, &rd.pc_core))) return rc;
+    if ((rc = sco_upload(allocs, rh.Ar[q].src, &rd.srcAr[q]))) return rc;
+  if ((rc = sco_upload(allocs, rh.pc_ptr, &rd.pc_ptr))) return rc;
+  if ((rc = sco_upload(allocs, rh.pc_pos, &rd.pc_pos))) return rc;
+  if ((rc = sco_upload(allocs, rh.pc_core, &rd.pc_core))) return rc;
   return SCO_OK;
 }
 
 template <int TR, int TC, int CW, bool ADAPT, int NS = 2, int LAY = 0>
 static int rl_launch_k(const RlArgs &ra, int batch, size_t lds, hipStream_t st) {
-  // hipFuncSetAttribute applies to the current device only
   static bool attr_done[64] = {};
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  dev_ &= 63;
-  if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                108 * 1024));
-    attr_done[dev_] = true;
-  }
+  SCO_LDS_ATTR((qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY>), 108 * 1024, attr_done);
   hipLaunchKernelGGL((qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY>), dim3(batch), dim3(LT), lds, st, ra);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
@@ -1459,7 +1447,7 @@ int rl_launch(const AdmmArgs &a, const RlHost &rh, const RlDev &rd, hipStream_t 
   RlArgs ra;
   ra.n = d.n; ra.m = d.m; ra.n_e = d.n_e; ra.n_c = d.n_c; ra.nnzA = d.nnzA; ra.nnzP = d.nnzP;
   ra.max_iter = a.max_iter; ra.check = a.check; ra.b0 = d.b0; ra.list = d.list;
-  const int nwg = d.nb > 0 ? d.nb : d.batch;
+  const int nwg = qp_launch_nwg(d);
   ra.sigma = a.sigma; ra.alpha = a.alpha; ra.eps_abs = a.eps_abs; ra.eps_rel = a.eps_rel;
   ra.eps_prim_inf = a.eps_prim_inf; ra.eps_dual_inf = a.eps_dual_inf;
   ra.off = rd.off; ra.role = rd.role; ra.srcAc = rd.srcAc;

@@ -1217,7 +1217,7 @@ __global__ void qp_wv_need_kernel(int b0, const int *list, int nb, const int *se
 }
 
 int wv_launch_need(const AdmmArgs &aa, const int *setup_mask, const WvDev &wd, hipStream_t st) {
-  const int nwg = aa.d.nb > 0 ? aa.d.nb : aa.d.batch;
+  const int nwg = qp_launch_nwg(aa.d);
   hipLaunchKernelGGL(qp_wv_need_kernel, dim3((nwg + 255) / 256), dim3(256), 0, st, aa.d.b0, aa.d.list, nwg, setup_mask, aa.d.active,
                      wd.w_ready, wd.rl_need);
   SCO_HIP(hipGetLastError());
@@ -1226,7 +1226,7 @@ int wv_launch_need(const AdmmArgs &aa, const int *setup_mask, const WvDev &wd, h
 
 int wv_launch_factor(const AdmmArgs &aa, const int *setup_mask, const WvHost &wh, const WvDev &wd, hipStream_t st) {
   WvArgs a; wv_fill_args(aa, wh, wd, setup_mask, a);
-  const int nwg = aa.d.nb > 0 ? aa.d.nb : aa.d.batch;
+  const int nwg = qp_launch_nwg(aa.d);
   hipLaunchKernelGGL(qp_wv_factor_kernel, dim3(nwg), dim3(WV_T), 0, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
@@ -1235,13 +1235,7 @@ int wv_launch_factor(const AdmmArgs &aa, const int *setup_mask, const WvHost &wh
 template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
 static int wv_launch_k(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
   static bool attr_done[64] = {};
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  dev_ &= 63;
-  if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    attr_done[dev_] = true;
-  }
+  SCO_LDS_ATTR((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>), 64 * 1024, attr_done);
   hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>), dim3(nwg), dim3(WV_T), lds, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
@@ -1256,7 +1250,7 @@ static int wv_launch_one(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
 
 int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t st) {
   WvArgs a; wv_fill_args(aa, wh, wd, nullptr, a);
-  const int nwg = aa.d.nb > 0 ? aa.d.nb : aa.d.batch;
+  const int nwg = qp_launch_nwg(aa.d);
   // the LDS request also fixes how many problems share a CU: at most 4 (one wavefront per SIMD)
   const size_t lds = std::max(wh.lds_bytes, (size_t)36 * 1024);      // (36 KB: never a fifth workgroup on a CU)
   if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3) return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps

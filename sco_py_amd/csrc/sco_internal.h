@@ -3,12 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
 
 #include "../../include/sco_hip.h"
 #include "qp_plan.h"
+#include "qp_tier.h"
 
 #define SCO_INFTY 1e30
 #define SCO_MIN_SCALING 1e-4
@@ -46,6 +48,47 @@ struct ScoDeviceGuard {
   ScoDeviceGuard sco_guard_(dev);                                             \
   if (!sco_guard_.ok) return sco_hip_fail(hipGetLastError(), "hipSetDevice")
 
+// ---- host glue shared by the tier files -------------------------------------
+// A vector as a device array, entered in `allocs` (freed with the handle); an empty vector still gets an allocation.
+template <typename T>
+inline int sco_upload(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
+  void *p = nullptr;
+  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+  SCO_HIP(hipMalloc(&p, bytes));
+  allocs.push_back(p);
+  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = (const T *)p;
+  return SCO_OK;
+}
+// A zeroed device array of `count` elements, entered in `allocs`.
+template <typename T>
+inline int sco_alloc_zeroed(std::vector<void *> &allocs, size_t count, T **out) {
+  void *p = nullptr;
+  size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  SCO_HIP(hipMalloc(&p, bytes));
+  SCO_HIP(hipMemset(p, 0, bytes));
+  allocs.push_back(p);
+  *out = (T *)p;
+  return SCO_OK;
+}
+// The dynamic-LDS limit of a kernel, raised once per device (hipFuncSetAttribute applies to the current device only).
+// attr_done: a static array of the calling launch helper, one per kernel instantiation; `what`: the call as the error
+// text of a failure names it (SCO_LDS_ATTR spells it the way the launch helpers' own SCO_HIP lines did).
+inline int sco_lds_attr(const void *kernel, int bytes, bool (&attr_done)[64], const char *what) {
+  int dev_ = 0;
+  (void)hipGetDevice(&dev_);
+  dev_ &= 63;
+  if (!attr_done[dev_]) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return sco_hip_fail(e, what);
+    attr_done[dev_] = true;
+  }
+  return SCO_OK;
+}
+#define SCO_LDS_ATTR(kernel, bytes, attr_done)                                                                             \
+  SCO_TRY(sco_lds_attr((const void *)kernel, bytes, attr_done,                                                             \
+                       "hipFuncSetAttribute((const void *)" #kernel ", hipFuncAttributeMaxDynamicSharedMemorySize, " #bytes ")"))
+
 // Device-side view of one batched QP: plans (shared) + per-problem value arrays.
 struct QpDev {
   int n, m, nnzP, nnzA, n_e, n_c, ncpl, nS, batch;
@@ -77,6 +120,8 @@ struct QpDev {
   double *rho_b;
   int *rflag, *smask, *nupd, *amask;   // amask: problems still parked (sco_qp_solve's own loop)
 };
+// workgroups of a per-problem kernel that honours the launch window
+inline int qp_launch_nwg(const QpDev &d) { return d.nb > 0 ? d.nb : d.batch; }
 
 // ---- fast ADMM path (sco_admm_fast.hip) ------------------------------------
 // Sliced-ELL image of a sparse operator: slices of 64 items, entry k of item
@@ -120,6 +165,7 @@ struct RegHost {
 };
 struct RegDev { const unsigned short *off; const int *role; const int *srcAc, *srcAr, *srcCa, *srcCe; };
 int reg_caps_for(const QpPlan &pl, int *CW, int *RW, int *PX);
+size_t reg_static_lds();              // static LDS of qp_admm_reg_kernel, bytes (the dynamic part: RegHost::lds_bytes)
 bool reg_plan_build(const QpPlan &pl, int CW, int RW, int PX, RegHost &rh);
 int reg_upload(const RegHost &rh, std::vector<void *> &allocs, RegDev &rd);
 int reg_launch(const AdmmArgs &a, const RegHost &rh, const RegDev &rd, hipStream_t st);
@@ -141,6 +187,7 @@ struct RlHost {
   std::vector<int> role, pc_ptr, pc_pos, pc_core;
 };
 struct RlDev { const unsigned short *off; const int *role, *srcAc, *srcAr[3], *pc_ptr, *pc_pos, *pc_core; };
+size_t rl_reported_static_lds();      // what sco_qp_info adds for qp_admm_rl_kernel's static LDS, bytes (see there: not today's size)
 bool rl_plan_build(const QpPlan &pl, RlHost &rh);
 int rl_upload(const RlHost &rh, std::vector<void *> &allocs, RlDev &rd);
 int rl_launch(const AdmmArgs &a, const RlHost &rh, const RlDev &rd, hipStream_t st);
@@ -203,28 +250,34 @@ int bt_upload(const BtHost &th, int batch, std::vector<void *> &allocs, BtDev &t
 int big_launch(const AdmmArgs &a, const int *setup_mask, int scaling, const int *Pp, const int *Pi, const BigHost &bh,
                const BigDev &bd, const BtHost *th, const BtDev *td, hipStream_t st, hipEvent_t ev_mid, hipEvent_t mid2);
 
-struct sco_qp {
-  int device = 0;
-  QpPlan plan;
-  BigHost big;
-  BigDev bigd{};
-  bool use_big = false;
-  BtHost bt;
-  BtDev btd{};
-  bool use_bt = false;
-  RlHost rl;
-  RlDev rld{};
-  bool use_rl = false;
-  WvHost wv;
-  WvDev wvd{};
+// Everything sco_qp_create decides about a handle before it allocates (qp_choose_tiers, sco_qp.hip: host code, no HIP
+// call).  Of the tier plans only those the handle can launch are built: the global-memory tier (and its structured form),
+// or the ONE on-chip kernel that runs -- the first of row-local, register-offset, sliced-ELL whose plan fits, else the
+// generic kernel -- and the wavefront tier beside the row-local kernel.
+struct QpTiers {
+  QpPlan plan;                         // (after the second analysis, where the global-memory tier asked for one)
+  size_t lds_setup = 0, lds_admm = 0;  // dynamic LDS of qp_setup_kernel (with the packed S) and qp_admm_kernel
+  bool factor_cholesky = false;        // SCO_QP_FACTOR_CHOLESKY=1: W by Cholesky + triangular inverse (cross-check)
+  bool use_big = false, use_bt = false;
+  int kern = QP_K_GENERIC;             // QpKernel: the on-chip ADMM kernel of this handle (!use_big)
   bool use_wv = false;
-  int cus = 0;                         // compute units of the device (tier choice by batch size)
+  BigHost big;
+  BtHost bt;
+  RlHost rl;
+  WvHost wv;
   RegHost reg;
-  RegDev regd{};
-  bool use_reg = false;
   FastHost fast;
+};
+
+struct sco_qp : QpTiers {
+  int device = 0;
+  int cus = 0;                         // compute units of the device (tier choice by batch size)
+  BigDev bigd{};
+  BtDev btd{};
+  RlDev rld{};
+  WvDev wvd{};
+  RegDev regd{};
   FastDev fastd{};
-  bool use_fast = false;
   QpDev d{};
   const int *Pp_dev = nullptr, *Pi_dev = nullptr;   // device copies of the P triu pattern
   hipStream_t stream = nullptr;
@@ -232,8 +285,6 @@ struct sco_qp {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   std::vector<void *> allocs;
   bool loaded = false, solved_once = false;
-  bool factor_cholesky = false;        // SCO_QP_FACTOR_CHOLESKY=1: W by Cholesky + triangular inverse (cross-check)
-  size_t lds_setup = 0, lds_admm = 0;
   double last_ms[2] = {0, 0};
 };
 
@@ -268,8 +319,6 @@ struct QpGroup {                                                                
 int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup_mask, const int *active_dev,
                          int slice, hipEvent_t mid, int *sliced, const QpGroup *grp = nullptr);
 bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st);
-int sco_qp_adaptive_interval(const sco_qp_settings *st);
-int sco_wv_min_live(int cus, bool adaptive = false);      // fewest live problems for which a round runs on the wavefront tier
 bool sco_qp_has_wv(const sco_qp *qp);
 int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out);      // iterations run by the wavefront kernel since the reset
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st);   // the handle holds the wavefront tier and these settings can use it

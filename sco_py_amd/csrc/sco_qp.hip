@@ -240,7 +240,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void qp_setup_kernel(SetupArgs a) {
 // exactly when the chains are long) and added with lane shuffles in a fixed order; 16 wavefronts hide the rest.
 // (The 256-thread single-chain version took 2.9 M cycles per 140 x 140 core, profiles/r01_setup_stamps.txt.)
 // --------------------------------------------------------------------------
-#define SCO_FACTOR_BLOCK 1024
+// (SCO_FACTOR_BLOCK = 1024 threads: qp_tier.h, the launch planner picks the sweep instantiation from it)
 
 __device__ __forceinline__ int lanes_per_row(int rows) {
   int l = 64;
@@ -720,34 +720,61 @@ __global__ void qp_rho_init_kernel(RhoInitArgs a) {
 // --------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------
-template <typename T>
-static int dev_upload(sco_qp *qp, const std::vector<T> &v, const T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  qp->allocs.push_back(p);
-  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T *)p;
-  return SCO_OK;
-}
-template <typename T>
-static int dev_alloc(sco_qp *qp, size_t count, T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  SCO_HIP(hipMemset(p, 0, bytes));
-  qp->allocs.push_back(p);
-  *out = (T *)p;
-  return SCO_OK;
-}
+static const size_t LDS_CAP = 160 * 1024;     // LDS of a CU
 
 static size_t setup_lds_doubles(const QpPlan &pl) {
   return (size_t)pl.nnzP + pl.nnzA + 2 * (size_t)pl.n + pl.m + pl.n + pl.m + pl.ncpl + NWAVE * 2 +
          (size_t)pl.n_c * (pl.n_c + 1) / 2;
 }
 
-static int qp_create_impl(sco_qp *qp, int device, int batch, int n, int m, const int *Pp, const int *Pi,
-                          const int *Ap, const int *Ai, hipStream_t stream);
+// Step 1 of sco_qp_create: everything that is decided about the handle, from the pattern and the switches alone.  No HIP
+// call: sco_debug_plan_tiers runs it on a machine without a GPU.
+static int qp_choose_tiers(int n, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai, const QpCreateEnv &env,
+                           QpTiers &t) {
+  t.factor_cholesky = env.factor_cholesky;
+  int rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, env.no_elim ? 0 : 1, t.plan);
+  if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
+  const QpPlan &pl = t.plan;
+  t.lds_setup = setup_lds_doubles(pl) * sizeof(double);
+  t.lds_admm = admm_lds_doubles(n, m, pl.nnzA, pl.n_e, pl.n_c, pl.ncpl) * sizeof(double) + (size_t)m * sizeof(int);
+  if (t.lds_setup > LDS_CAP || t.lds_admm > LDS_CAP || pl.n_c > SCO_BLOCK || env.force_big) {
+    // working set beyond a CU's LDS: the global-memory tier (sco_qp_big.hip)
+    bool ok_big = pl.n_c <= 1024 && big_plan_build(pl, t.big);
+    if (!ok_big && !env.no_elim) {
+      // the global-memory kernels keep an eliminated variable and its (at most two) rows in one thread:
+      // send variables with more rows to the core and analyse again
+      rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, 2, t.plan);
+      if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
+      t.big = BigHost();
+      ok_big = pl.n_c <= 1024 && big_plan_build(pl, t.big);
+    }
+    if (!ok_big) {
+      char buf[256];
+      snprintf(buf, sizeof buf, "sco_qp_create: pattern not supported (setup %zu B, admm %zu B of LDS, core %d)",
+               t.lds_setup, t.lds_admm, pl.n_c);
+      sco_set_error(buf); return SCO_ERR_CAPACITY;
+    }
+    t.use_big = true;
+    t.use_bt = !env.no_bt && bt_plan_build(pl, t.big, t.bt);
+    return SCO_OK;
+  }
+  // on-chip: the first ADMM kernel whose plan fits the pattern is the one this handle runs
+  int CW = 0, RW = 0, PX = 0;
+  if (!env.no_rl && rl_plan_build(pl, t.rl)) {
+    t.kern = QP_K_RL;
+    // wavefront tier (one wavefront per problem, block-tridiagonal core solve): patterns of trajectory penalty QPs; it
+    // needs the row-local kernel beside it for problems whose values leave the penalty-QP structure, and the Gauss-Jordan
+    // inversion.  The opt-in extensions (warm start, adaptive rho) run on it too
+    t.use_wv = !env.factor_cholesky && !env.no_wv && wv_plan_build(pl, t.wv);
+  } else if (!env.no_reg && reg_caps_for(pl, &CW, &RW, &PX) && reg_plan_build(pl, CW, RW, PX, t.reg)) {
+    t.kern = QP_K_REG;
+  } else if (!env.no_fast && fast_plan_build(pl, t.fast)) {
+    t.kern = QP_K_FAST;
+  }
+  return SCO_OK;
+}
+
+static int qp_alloc_upload(sco_qp *qp, int device, int batch, hipStream_t stream);
 
 int sco_qp_create_on_stream(int device, int batch, int n, int m, const int *Pp, const int *Pi,
                             const int *Ap, const int *Ai, hipStream_t stream, sco_qp **out) {
@@ -763,45 +790,18 @@ int sco_qp_create_on_stream(int device, int batch, int n, int m, const int *Pp, 
   SCO_ON_DEVICE(device);
   sco_qp *qp = new sco_qp();
   qp->device = device;
-  const int rc = qp_create_impl(qp, device, batch, n, m, Pp, Pi, Ap, Ai, stream);
+  int rc = qp_choose_tiers(n, m, Pp, Pi, Ap, Ai, qp_create_env(), *qp);
+  if (!rc) rc = qp_alloc_upload(qp, device, batch, stream);
   if (rc) { sco_qp_destroy(qp); return rc; }      // frees whatever had been allocated
   *out = qp;
   return SCO_OK;
 }
 
-static int qp_create_impl(sco_qp *qp, int device, int batch, int n, int m, const int *Pp, const int *Pi,
-                          const int *Ap, const int *Ai, hipStream_t stream) {
-  { const char *fc = getenv("SCO_QP_FACTOR_CHOLESKY"); qp->factor_cholesky = fc && fc[0] == '1'; }
-  const char *no_elim = getenv("SCO_QP_NO_ELIM");
-  int rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, (no_elim && no_elim[0] == '1') ? 0 : 1, qp->plan);
-  if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
+// Step 2: stream, events, the device arrays and the images of the tiers qp_choose_tiers chose.
+static int qp_alloc_upload(sco_qp *qp, int device, int batch, hipStream_t stream) {
   const QpPlan &pl = qp->plan;
+  const int n = pl.n, m = pl.m;
   (void)hipDeviceGetAttribute(&qp->cus, hipDeviceAttributeMultiprocessorCount, device);
-  qp->lds_setup = setup_lds_doubles(pl) * sizeof(double);
-  qp->lds_admm = admm_lds_doubles(n, m, pl.nnzA, pl.n_e, pl.n_c, pl.ncpl) * sizeof(double) + (size_t)m * sizeof(int);
-  const size_t lds_cap = 160 * 1024;
-  const char *force_big = getenv("SCO_QP_FORCE_BIG");
-  if (qp->lds_setup > lds_cap || qp->lds_admm > lds_cap || pl.n_c > SCO_BLOCK || (force_big && force_big[0] == '1')) {
-    // working set beyond a CU's LDS: the global-memory tier (sco_qp_big.hip)
-    bool ok_big = pl.n_c <= 1024 && big_plan_build(pl, qp->big);
-    if (!ok_big && !(no_elim && no_elim[0] == '1')) {
-      // the global-memory kernels keep an eliminated variable and its (at most two) rows in one thread:
-      // send variables with more rows to the core and analyse again
-      rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, 2, qp->plan);
-      if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
-      qp->big = BigHost();
-      ok_big = pl.n_c <= 1024 && big_plan_build(pl, qp->big);
-    }
-    if (!ok_big) {
-      char buf[256];
-      snprintf(buf, sizeof buf, "sco_qp_create: pattern not supported (setup %zu B, admm %zu B of LDS, core %d)",
-               qp->lds_setup, qp->lds_admm, pl.n_c);
-      sco_set_error(buf); return SCO_ERR_CAPACITY;
-    }
-    qp->use_big = true;
-    const char *no_bt = getenv("SCO_QP_NO_BT");
-    qp->use_bt = !(no_bt && no_bt[0] == '1') && bt_plan_build(pl, qp->big, qp->bt);
-  }
   if (stream) { qp->stream = stream; qp->own_stream = false; }
   else { SCO_HIP(hipStreamCreate(&qp->stream)); qp->own_stream = true; }
   for (auto &e : qp->ev) SCO_HIP(hipEventCreate(&e));
@@ -809,18 +809,16 @@ static int qp_create_impl(sco_qp *qp, int device, int batch, int n, int m, const
   QpDev &d = qp->d;
   d.n = n; d.m = m; d.nnzP = pl.nnzP; d.nnzA = pl.nnzA; d.n_e = pl.n_e; d.n_c = pl.n_c;
   d.ncpl = pl.ncpl; d.nS = pl.nS; d.batch = batch; d.active = nullptr;
-#define UP(field, vec) { int r_ = dev_upload<int>(qp, pl.vec, &d.field); if (r_) return r_; }
-  UP(Ap, Ap) UP(Ai, Ai) UP(Rp, Rp) UP(Rj, Rj) UP(Rpos, Rpos) UP(Fp, Fp) UP(Fi, Fi) UP(Fpos, Fpos) UP(Pdiag, Pdiag)
-  UP(elim_var, elim_var) UP(core_var, core_var) UP(elim_of, elim_of) UP(core_of, core_of)
-  UP(e_ptr, e_ptr) UP(pair_core, pair_core) UP(pair_elim, pair_elim) UP(cp_ptr, cp_ptr) UP(cp_row, cp_row)
-  UP(cp_pa, cp_pa) UP(cp_pe, cp_pe) UP(a_ptr, a_ptr) UP(a_pair, a_pair)
-  UP(s_a, s_a) UP(s_b, s_b) UP(s_ppos, s_ppos) UP(sa_ptr, sa_ptr) UP(sa_row, sa_row) UP(sa_pa, sa_pa) UP(sa_pb, sa_pb)
-  UP(ss_ptr, ss_ptr) UP(ss_k1, ss_k1) UP(ss_k2, ss_k2) UP(ss_e, ss_e)
+#define UP(field) SCO_TRY(sco_upload<int>(qp->allocs, pl.field, &d.field));
+  UP(Ap) UP(Ai) UP(Rp) UP(Rj) UP(Rpos) UP(Fp) UP(Fi) UP(Fpos) UP(Pdiag)
+  UP(elim_var) UP(core_var) UP(elim_of) UP(core_of)
+  UP(e_ptr) UP(pair_core) UP(pair_elim) UP(cp_ptr) UP(cp_row) UP(cp_pa) UP(cp_pe) UP(a_ptr) UP(a_pair)
+  UP(s_a) UP(s_b) UP(s_ppos) UP(sa_ptr) UP(sa_row) UP(sa_pa) UP(sa_pb) UP(ss_ptr) UP(ss_k1) UP(ss_k2) UP(ss_e)
 #undef UP
-  { int r_ = dev_upload<int>(qp, pl.Pp, &qp->Pp_dev); if (r_) return r_; }
-  { int r_ = dev_upload<int>(qp, pl.Pi, &qp->Pi_dev); if (r_) return r_; }
+  SCO_TRY(sco_upload<int>(qp->allocs, pl.Pp, &qp->Pp_dev));
+  SCO_TRY(sco_upload<int>(qp->allocs, pl.Pi, &qp->Pi_dev));
   const size_t B = (size_t)batch;
-#define AL(field, count) { int r_ = dev_alloc(qp, (count), &d.field); if (r_) return r_; }
+#define AL(field, count) SCO_TRY(sco_alloc_zeroed(qp->allocs, (count), &d.field));
   AL(Pval, B * pl.nnzP) AL(q, B * n) AL(Aval, B * pl.nnzA) AL(l, B * m) AL(u, B * m) AL(w, B * m)
   AL(Ps, B * pl.nnzP) AL(As, B * pl.nnzA) AL(qs, B * n) AL(ls, B * m) AL(us, B * m) AL(D, B * n) AL(E, B * m)
   AL(cscale, B) AL(rho, B * m) AL(kee_inv, B * pl.n_e) AL(cpl, B * pl.ncpl) AL(W, (qp->use_bt ? 1 : B) * pl.n_c * pl.n_c)
@@ -828,52 +826,18 @@ static int qp_create_impl(sco_qp *qp, int device, int batch, int n, int m, const
   AL(prog, B) AL(sx, B * n) AL(sz, B * m) AL(sy, B * m) AL(st, B * m) AL(sg, B * pl.n_e)
   AL(rho_b, B) AL(rflag, B) AL(smask, B) AL(nupd, B) AL(amask, B)
 #undef AL
-  SCO_HIP(hipFuncSetAttribute((const void *)qp_setup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-  SCO_HIP(hipFuncSetAttribute((const void *)qp_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-  SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+  SCO_HIP(hipFuncSetAttribute((const void *)qp_setup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP));
+  SCO_HIP(hipFuncSetAttribute((const void *)qp_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP));
+  SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP));
   if (qp->use_big) {
-    int r_ = big_upload(qp->big, qp->use_bt ? 1 : batch, qp->allocs, qp->bigd);   // dense workspace unused by bt
-    if (r_) return r_;
-    if (qp->use_bt && (r_ = bt_upload(qp->bt, batch, qp->allocs, qp->btd))) return r_;
+    SCO_TRY(big_upload(qp->big, qp->use_bt ? 1 : batch, qp->allocs, qp->bigd));   // dense workspace unused by bt
+    if (qp->use_bt) SCO_TRY(bt_upload(qp->bt, batch, qp->allocs, qp->btd));
     return SCO_OK;
   }
-  {
-    const char *no_rl = getenv("SCO_QP_NO_RL");
-    if (!(no_rl && no_rl[0] == '1') && rl_plan_build(pl, qp->rl)) {
-      int r_ = rl_upload(qp->rl, qp->allocs, qp->rld);
-      if (r_) return r_;
-      qp->use_rl = true;
-    }
-  }
-  {
-    // wavefront tier (one wavefront per problem, block-tridiagonal core solve): patterns of trajectory penalty QPs; it
-    // needs the row-local tier beside it for problems whose values leave the penalty-QP structure.  The opt-in extensions
-    // (warm start, adaptive rho) run on it too
-    const char *no_wv = getenv("SCO_QP_NO_WV");
-    const bool want_wv = !(no_wv && no_wv[0] == '1');
-    if (qp->use_rl && !qp->factor_cholesky && want_wv && wv_plan_build(pl, qp->wv)) {
-      int r_ = wv_upload(qp->wv, batch, n, m, qp->allocs, qp->wvd);
-      if (r_) return r_;
-      qp->use_wv = true;
-    }
-  }
-  {
-    const char *no_reg = getenv("SCO_QP_NO_REG");
-    int CW = 0, RW = 0, PX = 0;
-    if (!(no_reg && no_reg[0] == '1') && reg_caps_for(pl, &CW, &RW, &PX) && reg_plan_build(pl, CW, RW, PX, qp->reg)) {
-      int r_ = reg_upload(qp->reg, qp->allocs, qp->regd);
-      if (r_) return r_;
-      qp->use_reg = true;
-    }
-  }
-  {
-    const char *no_fast = getenv("SCO_QP_NO_FAST");
-    if (!(no_fast && no_fast[0] == '1') && fast_plan_build(pl, qp->fast)) {
-      int r_ = fast_upload(qp->fast, qp->allocs, qp->fastd);
-      if (r_) return r_;
-      qp->use_fast = true;
-    }
-  }
+  if (qp->kern == QP_K_RL) SCO_TRY(rl_upload(qp->rl, qp->allocs, qp->rld));
+  if (qp->use_wv) SCO_TRY(wv_upload(qp->wv, batch, n, m, qp->allocs, qp->wvd));
+  if (qp->kern == QP_K_REG) SCO_TRY(reg_upload(qp->reg, qp->allocs, qp->regd));
+  if (qp->kern == QP_K_FAST) SCO_TRY(fast_upload(qp->fast, qp->allocs, qp->fastd));
   return SCO_OK;
 }
 
@@ -933,31 +897,6 @@ int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, 
   return sco_qp_launch_sliced(qp, st, active_dev, active_dev, 0, mid, nullptr);
 }
 
-// fewest problems of a launch for which the wavefront tier is the faster one (SCO_WV_MIN_PER_CU: problems per CU, default 2.75;
-// 3.0 until the SQP loop learnt mixed rounds, which fill the CUs such a round leaves free: on the 1024-problem 7x20 step 2.5 .. 3.0
-// give the same schedule and 2.0 and below a slower one, a step that starts with 700 problems is a quarter faster on this tier
-// (profiles/mixed_rounds.md) -- but the schedule tests pin a 700-problem batch, 2.73 per CU of 256, to row-local rounds).
-// With adaptive rho the default is "never": a launch then goes by the size of the BATCH, not by how many of its problems are
-// still alive (no round selection), a solve parks at every rho change and the launches are short and mostly narrow.  Measured
-// on `bench.py --beyond` (1024 problems, 4 per CU, 122 launches of ~100 iterations per step): 503 ms of ADMM launches per
-// step on this tier against 285 ms on the row-local kernel (profiles/wv_extensions.md).  The variable still applies when set.
-int sco_wv_min_live(int cus, bool adaptive) {
-  const char *e = getenv("SCO_WV_MIN_PER_CU");
-  if (!e && adaptive) return INT_MAX;
-  const double live = (e ? atof(e) : 2.75) * (cus > 0 ? cus : 256);
-  return live >= (double)INT_MAX ? INT_MAX : (int)live;
-}
-
-int sco_qp_adaptive_interval(const sco_qp_settings *st) {
-  if (st->adaptive_rho_interval > 0) {
-    // park points sit on termination checks
-    if (st->check_termination > 0)
-      return std::max(1, (st->adaptive_rho_interval + st->check_termination / 2) / st->check_termination) * st->check_termination;
-    return st->adaptive_rho_interval;
-  }
-  return st->check_termination > 0 ? 4 * st->check_termination : 100;
-}
-
 int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
   *out = 0;
   if (!qp->use_wv) return SCO_OK;
@@ -968,157 +907,150 @@ void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st) { if (qp->use_wv) (void)h
 bool sco_qp_has_wv(const sco_qp *qp) { return qp->use_wv; }
 bool sco_qp_can_adapt(const sco_qp *qp) { return !(qp->use_big && !qp->use_bt); }
 
-// Launch windows and index lists (QpGroup) exist for the paths the bench workloads take: row-local ADMM kernel with
-// the Gauss-Jordan inversion, and the structured global-memory tier; fixed rho.
-bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st) {
-  if (st->adaptive_rho) return false;
-  if (qp->use_big) return qp->use_bt;                      // structured global-memory tier
-  return qp->use_rl && !qp->factor_cholesky;
+// ---- a launch: planned on plain numbers (qp_tier.h), then issued step by step ------------------------------------
+// what the planner needs to know of the handle and the settings
+static QpLaunchIn qp_launch_in(const sco_qp *qp, const sco_qp_settings *st) {
+  QpLaunchIn in;
+  in.kern = qp->kern; in.use_big = qp->use_big; in.use_bt = qp->use_bt; in.use_wv = qp->use_wv;
+  in.factor_cholesky = qp->factor_cholesky; in.batch = qp->d.batch; in.n_c = qp->d.n_c; in.cus = qp->cus;
+  in.adaptive_rho = st->adaptive_rho; in.adaptive_rho_interval = st->adaptive_rho_interval;
+  in.adaptive_rho_tolerance = st->adaptive_rho_tolerance; in.check_termination = st->check_termination; in.max_iter = st->max_iter;
+  return in;
+}
+
+bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st) { return qp_supports_windows(qp_launch_in(qp, st)); }
+
+static QpLaunchPlan qp_plan_launch(const sco_qp *qp, const sco_qp_settings *st, const int *setup_mask, int slice, const QpGroup *grp) {
+  QpLaunchIn in = qp_launch_in(qp, st);
+  in.slice = slice;
+  in.mask = setup_mask == SCO_MASK_ALL ? QP_MASK_ALL : setup_mask == SCO_MASK_NONE ? QP_MASK_NONE : QP_MASK_ARRAY;
+  in.wv_min = sco_wv_min_live(qp->cus, st->adaptive_rho != 0);
+  if (grp) {
+    in.window = true; in.b0 = grp->b0; in.nb = grp->nb; in.tier = grp->tier; in.has_list = grp->list != nullptr;
+    in.side_b0 = grp->side_b0; in.side_nb = grp->side_nb; in.side_slices = grp->side_slices;
+    in.side_ready = grp->side_stream && grp->side_ev[0] && grp->side_ev[1] && grp->side_ev[2];
+  }
+  return qp_launch_plan(in);
+}
+
+// adaptive rho: the problems that start a QP get the initial rho and their setup flag (the parked ones keep what the ADMM
+// kernel left when it parked them)
+static int qp_launch_rho_init(const QpDev &d, const int *setup_mask, double rho, hipStream_t stream) {
+  RhoInitArgs ra{d, setup_mask == SCO_MASK_ALL ? nullptr : setup_mask, setup_mask == SCO_MASK_ALL ? 1 : 0, rho};
+  hipLaunchKernelGGL(qp_rho_init_kernel, dim3((d.batch + 255) / 256), dim3(256), 0, stream, ra);
+  SCO_HIP(hipGetLastError());
+  return SCO_OK;
+}
+
+// On-chip route, first half: scaling + reduced matrix (256 threads, S into the W buffer), then factor + inverse (1024
+// threads) for the problems of `setup_active` and those the plan's wv_launch_need case adds.
+static int qp_launch_setup_factor(sco_qp *qp, const QpLaunchPlan &pl, const sco_qp_settings *st, const AdmmArgs &aa,
+                                  const int *setup_active, const QpGroup *grp, hipStream_t stream) {
+  QpDev dsetup = aa.d; dsetup.active = setup_active;
+  const size_t ntri = (size_t)dsetup.n_c * (dsetup.n_c + 1) / 2;
+  SetupArgs sa{dsetup, qp->Pp_dev, qp->Pi_dev, st->rho, st->sigma, st->scaling, st->adaptive_rho ? 1 : 0};
+  hipLaunchKernelGGL(qp_setup_kernel, dim3(pl.nwg), dim3(SCO_BLOCK), qp->lds_setup - ntri * sizeof(double), stream, sa);
+  SCO_HIP(hipGetLastError());
+  // wavefront round: twisted block factorisation + the value test; the dense inverse below then runs for the problems that
+  // failed it only (adaptive rho: the factorisation runs over smask, the problems that start a QP or have changed rho)
+  if (pl.wv_now) SCO_TRY(wv_launch_factor(aa, setup_active, qp->wv, qp->wvd, stream));
+  if (pl.need == QP_NEED_SIDE) {
+    // mixed round: the side window's problems that start a QP, or whose QP the wavefront tier factored (W not formed yet),
+    // while the W buffer still holds S -- a problem that starts its QP on the row-local side keeps its factor G and may run
+    // on the wavefront tier in a later round
+    AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb;
+    SCO_TRY(wv_launch_need(as, setup_active, qp->wvd, stream));
+  } else if (pl.need == QP_NEED_WINDOW) {
+    // a row-local launch on a handle that also runs the wavefront tier: besides the problems that start a QP, the dense
+    // inverse is formed for the active ones whose QP was factored by that tier (their W buffer still holds S)
+    SCO_TRY(wv_launch_need(aa, setup_active, qp->wvd, stream));
+  }
+  if (pl.wv_now || pl.need != QP_NEED_NONE) dsetup.active = qp->wvd.rl_need;
+  if (pl.cholesky)
+    hipLaunchKernelGGL(qp_factor_kernel, dim3(dsetup.batch), dim3(SCO_FACTOR_BLOCK), (ntri + dsetup.n_c) * sizeof(double), stream, dsetup);
+  else if (pl.sweep_nt == 1) hipLaunchKernelGGL(qp_sweep_kernel<1>, dim3(pl.nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
+  else if (pl.sweep_nt == 2) hipLaunchKernelGGL(qp_sweep_kernel<2>, dim3(pl.nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
+  else hipLaunchKernelGGL(qp_sweep_kernel<3>, dim3(pl.nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
+  SCO_HIP(hipGetLastError());
+  return SCO_OK;
+}
+
+// Mixed round: two launches resident at once.  A row-local workgroup needs a whole CU and finds none once the wavefront
+// launch has spread over the chip, so the side launch is issued first and the wavefront launch is gated behind an event
+// recorded in front of it: it cannot be dispatched before the side stream has reached its launch.  Neither launch reads what
+// the other writes (disjoint problems), so neither can wait for the other; both streams join at the end.
+static int qp_launch_mixed(sco_qp *qp, const AdmmArgs &aa, const QpGroup *grp, hipStream_t stream) {
+  AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb; as.slice = grp->side_slices * aa.slice;
+  AdmmArgs aw = aa;
+  aw.d.b0 = grp->side_b0 == grp->b0 ? grp->b0 + grp->side_nb : grp->b0; aw.d.nb = grp->nb - grp->side_nb;
+  SCO_HIP(hipEventRecord(grp->side_ev[0], stream));
+  SCO_HIP(hipStreamWaitEvent(grp->side_stream, grp->side_ev[0], 0));
+  SCO_HIP(hipEventRecord(grp->side_ev[1], grp->side_stream));
+  SCO_TRY(rl_launch(as, qp->rl, qp->rld, grp->side_stream));
+  SCO_HIP(hipEventRecord(grp->side_ev[2], grp->side_stream));
+  SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[1], 0));
+  SCO_TRY(wv_launch(aw, qp->wv, qp->wvd, stream));
+  aw.skip = qp->wvd.ok;                        // the problems of the wavefront window that failed the value test
+  SCO_TRY(rl_launch(aw, qp->rl, qp->rld, stream));
+  SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[2], 0));
+  return SCO_OK;
+}
+
+// On-chip route, second half: the ADMM launches of the plan's sequence
+static int qp_launch_admm(sco_qp *qp, const QpLaunchPlan &pl, AdmmArgs aa, const QpGroup *grp, hipStream_t stream) {
+  switch (pl.admm) {
+    case QP_ADMM_MIXED: return qp_launch_mixed(qp, aa, grp, stream);
+    case QP_ADMM_WV_RL:
+      SCO_TRY(wv_launch(aa, qp->wv, qp->wvd, stream));
+      aa.skip = qp->wvd.ok;                      // the row-local kernel takes what the wavefront tier has left
+      return rl_launch(aa, qp->rl, qp->rld, stream);
+    case QP_ADMM_RL: return rl_launch(aa, qp->rl, qp->rld, stream);
+    case QP_ADMM_REG: return reg_launch(aa, qp->reg, qp->regd, stream);
+    case QP_ADMM_FAST: return fast_launch(aa, qp->fast, qp->fastd, stream);
+  }
+  hipLaunchKernelGGL(qp_admm_kernel, dim3(aa.d.batch), dim3(SCO_BLOCK), qp->lds_admm, stream, aa);
+  SCO_HIP(hipGetLastError());
+  return SCO_OK;
 }
 
 int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup_mask, const int *active_dev,
                          int slice, hipEvent_t mid, int *sliced, const QpGroup *grp) {
+  const QpLaunchPlan pl = qp_plan_launch(qp, st, setup_mask, slice, grp);
+  if (sliced && pl.slice >= 0) *sliced = pl.slice;
+  if (pl.rc) { sco_set_error(qp_launch_err_text(pl.err)); return pl.rc; }
   const bool adaptive = st->adaptive_rho != 0;
-  if (grp && (!sco_qp_supports_groups(qp, st) || grp->b0 < 0 || grp->nb <= 0 || grp->b0 + grp->nb > qp->d.batch)) {
-    sco_set_error("sco_qp_launch_sliced: launch window not supported by this handle's tier"); return SCO_ERR_STATE;
-  }
   hipStream_t stream = grp ? grp->stream : qp->stream;
-  if (adaptive) {
-    if (qp->use_big && !qp->use_bt) {
-      sco_set_error("adaptive_rho: the dense form of the global-memory tier cannot park a solve");
-      return SCO_ERR_CAPACITY;
-    }
-    if (!(st->adaptive_rho_tolerance > 1.0) || st->check_termination <= 0) {
-      sco_set_error("adaptive_rho needs adaptive_rho_tolerance > 1 and check_termination > 0"); return SCO_ERR_ARG;
-    }
-  }
-  // kernel of the on-chip tiers (every one of them parks and resumes a solve; the register-offset kernel since r03)
-  enum { K_RL, K_REG, K_FAST, K_GENERIC };
-  const int kern = qp->use_rl ? K_RL : qp->use_reg ? K_REG : qp->use_fast ? K_FAST : K_GENERIC;
-  const bool can_park = qp->use_big ? qp->use_bt : true;
-  if (!can_park || st->check_termination <= 0 || (slice <= 0 && !adaptive)) {
-    slice = 0;                                  // one launch per solve (always so on the dense global-memory form)
-  } else {
-    // slices end on a termination check; adaptive rho without time slicing parks only when rho changes
-    if (slice <= 0) slice = st->max_iter;
-    slice = std::max(1, (slice + st->check_termination - 1) / st->check_termination) * st->check_termination;
-  }
-  if (sliced) *sliced = slice;
   QpDev d = qp->d; d.active = active_dev;
-  QpDev dsetup = qp->d; dsetup.active = adaptive ? qp->d.smask : setup_mask;
-  if (grp) { d.b0 = dsetup.b0 = grp->b0; d.nb = dsetup.nb = grp->nb; d.list = dsetup.list = grp->list; }
-  const int nwg = grp ? grp->nb : d.batch;          // workgroups of the per-problem kernels
-  SetupArgs sa{dsetup, qp->Pp_dev, qp->Pi_dev, st->rho, st->sigma, st->scaling, adaptive ? 1 : 0};
+  if (grp) { d.b0 = grp->b0; d.nb = grp->nb; d.list = grp->list; }
+  const int *setup_active = adaptive ? qp->d.smask : setup_mask;     // the problems whose setup + factorisation run
   AdmmArgs aa{d, st->rho, st->sigma, st->alpha, st->eps_abs, st->eps_rel, st->eps_prim_inf, st->eps_dual_inf,
-              st->max_iter, st->check_termination, (st->warm_start && qp->solved_once) ? 1 : 0, slice,
-              adaptive ? 1 : 0, adaptive ? sco_qp_adaptive_interval(st) : 0, st->adaptive_rho_tolerance, nullptr};
-  // The wavefront tier runs parity mode and the opt-in extensions alike: a warm start only changes the start of a solve,
-  // adaptive rho runs its ADAPT instantiation, and the factorisation then runs over smask (dsetup.active), the problems
-  // that start a QP or have changed rho.
-  // It puts four problems on a CU at ~3.1 us per iteration each where the row-local kernel runs one at ~0.95 us: it is
-  // the faster way through a launch only with more than ~3 problems per CU to run (profiles/r04_wv.txt).  The SQP loop
-  // says per round which one it wants (QpGroup::tier, from its live count); a plain sco_qp_solve goes by the batch.
-  const bool wv_can = qp->use_wv;
-  const int wv_min = sco_wv_min_live(qp->cus, adaptive);
-  const bool mixed = grp && grp->tier == 3;
-  if (mixed) {
-    const bool at_end = grp->side_b0 == grp->b0 || grp->side_b0 + grp->side_nb == grp->b0 + grp->nb;
-    if (!wv_can || kern != K_RL || adaptive || slice <= 0 || !grp->list || grp->side_nb <= 0 || grp->side_nb >= grp->nb || !at_end ||
-        grp->side_slices <= 0 || !grp->side_stream || !grp->side_ev[0] || !grp->side_ev[1] || !grp->side_ev[2]) {
-      sco_set_error("sco_qp_launch_sliced: mixed round not supported by this handle or its side window is malformed"); return SCO_ERR_STATE;
-    }
-  }
-  const bool wv_now = wv_can && (grp && grp->tier ? grp->tier >= 2 : (grp ? grp->nb : d.batch) >= wv_min);
+              st->max_iter, st->check_termination, (st->warm_start && qp->solved_once) ? 1 : 0, pl.slice,
+              adaptive ? 1 : 0, pl.ad_interval, st->adaptive_rho_tolerance, nullptr};
   qp->solved_once = true;
   if (!grp) SCO_HIP(hipEventRecord(qp->ev[0], stream));
-  if (adaptive && setup_mask != SCO_MASK_NONE) {
-    // the problems that start a QP get the initial rho and their setup flag (the parked ones keep what the ADMM
-    // kernel left when it parked them)
-    RhoInitArgs ra{d, setup_mask == SCO_MASK_ALL ? nullptr : setup_mask, setup_mask == SCO_MASK_ALL ? 1 : 0, st->rho};
-    hipLaunchKernelGGL(qp_rho_init_kernel, dim3((d.batch + 255) / 256), dim3(256), 0, stream, ra);
-    SCO_HIP(hipGetLastError());
-  }
-  if (qp->use_big) {
-    int r_ = big_launch(aa, dsetup.active, st->scaling, qp->Pp_dev, qp->Pi_dev, qp->big, qp->bigd,
-                        qp->use_bt ? &qp->bt : nullptr, qp->use_bt ? &qp->btd : nullptr, stream, grp ? nullptr : qp->ev[1], mid);
-    if (r_) return r_;
-    if (!grp) SCO_HIP(hipEventRecord(qp->ev[2], stream));
-    return SCO_OK;
-  }
-  {
-    // scaling + reduced matrix (256 threads, S into the W buffer), then factor + inverse (1024 threads)
-    const size_t ntri = (size_t)d.n_c * (d.n_c + 1) / 2;
-    hipLaunchKernelGGL(qp_setup_kernel, dim3(nwg), dim3(SCO_BLOCK), qp->lds_setup - ntri * sizeof(double), stream, sa);
-    SCO_HIP(hipGetLastError());
-    if (wv_now) {
-      // twisted block factorisation + the value test; the dense inverse below then runs for the problems that failed it only
-      // (mixed round: for every problem of the window that starts a QP, the side window's too, while the W buffer still holds
-      // S -- a problem that starts its QP on the row-local side keeps its factor G and may run on this tier in a later round)
-      int r_ = wv_launch_factor(aa, dsetup.active, qp->wv, qp->wvd, stream);
-      if (r_) return r_;
-      if (mixed) {
-        // the side window's problems that start a QP, or whose QP this tier factored (W not formed yet): dense inverse below
-        AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb;
-        if ((r_ = wv_launch_need(as, dsetup.active, qp->wvd, stream))) return r_;
-      }
-      dsetup.active = qp->wvd.rl_need;
-    } else if (qp->use_wv) {
-      // a row-local launch on a handle that also runs the wavefront tier: besides the problems that start a QP, the dense
-      // inverse is formed for the active ones whose QP was factored by that tier (their W buffer still holds S)
-      int r_ = wv_launch_need(aa, dsetup.active, qp->wvd, stream);
-      if (r_) return r_;
-      dsetup.active = qp->wvd.rl_need;
-    }
-    if (qp->factor_cholesky)
-      hipLaunchKernelGGL(qp_factor_kernel, dim3(d.batch), dim3(SCO_FACTOR_BLOCK), (ntri + d.n_c) * sizeof(double), stream, dsetup);
-    else {
-      const int nb = (d.n_c + 3) / 4, ntiles = nb * (nb + 1) / 2;
-      if (ntiles <= SCO_FACTOR_BLOCK) hipLaunchKernelGGL(qp_sweep_kernel<1>, dim3(nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
-      else if (ntiles <= 2 * SCO_FACTOR_BLOCK) hipLaunchKernelGGL(qp_sweep_kernel<2>, dim3(nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
-      else hipLaunchKernelGGL(qp_sweep_kernel<3>, dim3(nwg), dim3(SCO_FACTOR_BLOCK), 0, stream, dsetup);
-    }
-    SCO_HIP(hipGetLastError());
-  }
-  if (!grp) SCO_HIP(hipEventRecord(qp->ev[1], stream));
-  if (mid) SCO_HIP(hipEventRecord(mid, stream));
-  if (kern == K_RL && mixed) {
-    // Two launches resident at once.  A row-local workgroup needs a whole CU and finds none once the wavefront launch has
-    // spread over the chip, so the side launch is issued first and the wavefront launch is gated behind an event recorded
-    // in front of it: it cannot be dispatched before the side stream has reached its launch.  Neither launch reads what the
-    // other writes (disjoint problems), so neither can wait for the other; both streams join below.
-    AdmmArgs as = aa; as.d.b0 = grp->side_b0; as.d.nb = grp->side_nb; as.slice = grp->side_slices * slice;
-    AdmmArgs aw = aa;
-    aw.d.b0 = grp->side_b0 == grp->b0 ? grp->b0 + grp->side_nb : grp->b0; aw.d.nb = grp->nb - grp->side_nb;
-    SCO_HIP(hipEventRecord(grp->side_ev[0], stream));
-    SCO_HIP(hipStreamWaitEvent(grp->side_stream, grp->side_ev[0], 0));
-    SCO_HIP(hipEventRecord(grp->side_ev[1], grp->side_stream));
-    int r_ = rl_launch(as, qp->rl, qp->rld, grp->side_stream);
-    if (r_) return r_;
-    SCO_HIP(hipEventRecord(grp->side_ev[2], grp->side_stream));
-    SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[1], 0));
-    if ((r_ = wv_launch(aw, qp->wv, qp->wvd, stream))) return r_;
-    aw.skip = qp->wvd.ok;                        // the problems of the wavefront window that failed the value test
-    if ((r_ = rl_launch(aw, qp->rl, qp->rld, stream))) return r_;
-    SCO_HIP(hipStreamWaitEvent(stream, grp->side_ev[2], 0));
-  } else if (kern == K_RL) {
-    if (wv_now) {
-      int r_ = wv_launch(aa, qp->wv, qp->wvd, stream);
-      if (r_) return r_;
-      aa.skip = qp->wvd.ok;                      // the row-local kernel takes what the wavefront tier has left
-    }
-    int r_ = rl_launch(aa, qp->rl, qp->rld, stream);
-    if (r_) return r_;
-  } else if (kern == K_REG) {
-    int r_ = reg_launch(aa, qp->reg, qp->regd, stream);
-    if (r_) return r_;
-  } else if (kern == K_FAST) {
-    int r_ = fast_launch(aa, qp->fast, qp->fastd, stream);
-    if (r_) return r_;
+  if (pl.rho_init) SCO_TRY(qp_launch_rho_init(d, setup_mask, st->rho, stream));
+  if (pl.route != QP_ROUTE_ONCHIP) {
+    SCO_TRY(big_launch(aa, setup_active, st->scaling, qp->Pp_dev, qp->Pi_dev, qp->big, qp->bigd, qp->use_bt ? &qp->bt : nullptr,
+                       qp->use_bt ? &qp->btd : nullptr, stream, grp ? nullptr : qp->ev[1], mid));
   } else {
-    hipLaunchKernelGGL(qp_admm_kernel, dim3(d.batch), dim3(SCO_BLOCK), qp->lds_admm, stream, aa);
-    SCO_HIP(hipGetLastError());
+    SCO_TRY(qp_launch_setup_factor(qp, pl, st, aa, setup_active, grp, stream));
+    if (!grp) SCO_HIP(hipEventRecord(qp->ev[1], stream));
+    if (mid) SCO_HIP(hipEventRecord(mid, stream));
+    SCO_TRY(qp_launch_admm(qp, pl, aa, grp, stream));
   }
   if (!grp) SCO_HIP(hipEventRecord(qp->ev[2], stream));
+  return SCO_OK;
+}
+
+// results of the last launch to the caller's buffers (any may be null); waits for the handle's stream
+static int qp_copy_back(const sco_qp *qp, double *x, double *y, int *status, int *iters, double *resid) {
+  const QpDev &d = qp->d; const size_t B = d.batch;
+  if (x) SCO_HIP(hipMemcpyAsync(x, d.x, B * d.n * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
+  if (y && d.m) SCO_HIP(hipMemcpyAsync(y, d.y, B * d.m * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
+  if (status) SCO_HIP(hipMemcpyAsync(status, d.status, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
+  if (iters) SCO_HIP(hipMemcpyAsync(iters, d.iters, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
+  if (resid) SCO_HIP(hipMemcpyAsync(resid, d.resid, B * 2 * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
+  SCO_HIP(hipStreamSynchronize(qp->stream));
   return SCO_OK;
 }
 
@@ -1154,23 +1086,13 @@ extern "C" int sco_qp_solve(sco_qp *qp, const sco_qp_settings *settings, double 
       if (!parked) break;
       SCO_HIP(hipMemcpyAsync(d.amask, prog.data(), B * sizeof(int), hipMemcpyHostToDevice, qp->stream));
     }
-    if (x) SCO_HIP(hipMemcpyAsync(x, d.x, B * d.n * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-    if (y && d.m) SCO_HIP(hipMemcpyAsync(y, d.y, B * d.m * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-    if (status) SCO_HIP(hipMemcpyAsync(status, d.status, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
-    if (iters) SCO_HIP(hipMemcpyAsync(iters, d.iters, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
-    if (resid) SCO_HIP(hipMemcpyAsync(resid, d.resid, B * 2 * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-    SCO_HIP(hipStreamSynchronize(qp->stream));
+    SCO_TRY(qp_copy_back(qp, x, y, status, iters, resid));
     qp->last_ms[0] = ms_setup; qp->last_ms[1] = ms_admm;
     return SCO_OK;
   }
   rc = sco_qp_launch(qp, settings, nullptr, nullptr);
   if (rc) return rc;
-  if (x) SCO_HIP(hipMemcpyAsync(x, d.x, B * d.n * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-  if (y && d.m) SCO_HIP(hipMemcpyAsync(y, d.y, B * d.m * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-  if (status) SCO_HIP(hipMemcpyAsync(status, d.status, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
-  if (iters) SCO_HIP(hipMemcpyAsync(iters, d.iters, B * sizeof(int), hipMemcpyDeviceToHost, qp->stream));
-  if (resid) SCO_HIP(hipMemcpyAsync(resid, d.resid, B * 2 * sizeof(double), hipMemcpyDeviceToHost, qp->stream));
-  SCO_HIP(hipStreamSynchronize(qp->stream));
+  SCO_TRY(qp_copy_back(qp, x, y, status, iters, resid));
   float ms0 = 0, ms1 = 0;
   SCO_HIP(hipEventElapsedTime(&ms0, qp->ev[0], qp->ev[1]));
   SCO_HIP(hipEventElapsedTime(&ms1, qp->ev[1], qp->ev[2]));
@@ -1187,10 +1109,21 @@ extern "C" int sco_qp_adaptive_info(sco_qp *qp, double *rho, int *updates) {
   return SCO_OK;
 }
 
+// LDS of a workgroup of the handle's ADMM kernel (0: the dense global-memory form keeps nothing there)
+static size_t qp_admm_lds_bytes(const sco_qp *qp) {
+  if (qp->use_big) return qp->use_bt ? qp->bt.lds_bytes : 0;
+  switch (qp->kern) {
+    case QP_K_RL: return rl_reported_static_lds() + qp->rl.lds_bytes;
+    case QP_K_REG: return reg_static_lds() + qp->reg.lds_bytes;
+    case QP_K_FAST: return qp->fast.lds_bytes;
+  }
+  return qp->lds_admm;
+}
+
 extern "C" int sco_qp_info(const sco_qp *qp, int info[4]) {
   if (!qp || !info) return SCO_ERR_ARG;
   info[0] = qp->plan.n_e; info[1] = qp->plan.n_c;
-  info[2] = (int)(qp->use_big ? (qp->use_bt ? qp->bt.lds_bytes : 0) : qp->use_rl ? 30208 + qp->rl.lds_bytes : qp->use_reg ? 44032 + qp->reg.lds_bytes : (qp->use_fast ? qp->fast.lds_bytes : qp->lds_admm)); info[3] = qp->plan.ncpl;
+  info[2] = (int)qp_admm_lds_bytes(qp); info[3] = qp->plan.ncpl;
   return SCO_OK;
 }
 
@@ -1243,12 +1176,27 @@ extern "C" int sco_debug_bt_plan(int *info) {
   info[0] = ok ? 1 : 0; info[1] = th.bs; info[2] = th.nb; info[3] = th.use_mfma ? 1 : 0; info[4] = th.mf_why; info[5] = (int)th.lds_bytes;
   return SCO_OK;
 }
-// Which ADMM tiers a handle holds: bit 0 row-local, 1 register-offset, 2 sliced-ELL, 3 global memory, 4 its structured form,
-// 5 wavefront tier, 6 the structured form builds its block normal matrices on the matrix cores (MFMA)
+// Which ADMM tiers a handle RUNS: bit 0 row-local, 1 register-offset, 2 sliced-ELL (at most one of the three: the handle's
+// on-chip kernel; none = the generic kernel), 3 global memory, 4 its structured form, 5 wavefront tier beside the row-local
+// kernel, 6 the structured form builds its block normal matrices on the matrix cores (MFMA).  (Bits 1 and 2 said "holds the
+// plan" while handles still built plans they could never launch.)
+static int qp_tier_mask(const QpTiers &t) {
+  return (t.kern == QP_K_RL ? 1 : 0) | (t.kern == QP_K_REG ? 2 : 0) | (t.kern == QP_K_FAST ? 4 : 0) | (t.use_big ? 8 : 0) |
+         (t.use_bt ? 16 : 0) | (t.use_wv ? 32 : 0) | ((t.use_bt && t.bt.use_mfma) ? 64 : 0);
+}
 extern "C" int sco_debug_qp_tiers(const sco_qp *qp) {
   if (!qp) return SCO_ERR_ARG;
-  return (qp->use_rl ? 1 : 0) | (qp->use_reg ? 2 : 0) | (qp->use_fast ? 4 : 0) | (qp->use_big ? 8 : 0) | (qp->use_bt ? 16 : 0) | (qp->use_wv ? 32 : 0) |
-         ((qp->use_bt && qp->bt.use_mfma) ? 64 : 0);
+  return qp_tier_mask(*qp);
+}
+// Host-only: the mask sco_debug_qp_tiers would give for a handle created now -- under the SCO_QP_* switches as they stand --
+// from the pattern last given to sco_debug_plan_build (whatever allow_elim was passed there)
+extern "C" int sco_debug_plan_tiers(int *mask) {
+  const QpPlan &p = g_dbg_plan;
+  if (!mask || p.n <= 0) return SCO_ERR_ARG;
+  QpTiers t;
+  SCO_TRY(qp_choose_tiers(p.n, p.m, p.Pp.data(), p.Pi.data(), p.Ap.data(), p.Ai.data(), qp_create_env(), t));
+  *mask = qp_tier_mask(t);
+  return SCO_OK;
 }
 // Iterations run by the wavefront kernel on this handle since the counter was last reset (only the SQP layer resets it): a
 // test reads it before and after a solve to see which problems that kernel really took.  0 on a handle without the tier.

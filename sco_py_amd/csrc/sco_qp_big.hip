@@ -1623,27 +1623,16 @@ __global__ __launch_bounds__(BTT) void qp_admm_bt_kernel(BigArgs a) {
 // --------------------------------------------------------------------------
 // host glue
 // --------------------------------------------------------------------------
-template <typename T>
-static int upb(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  SCO_HIP(hipMalloc(&p, bytes));
-  allocs.push_back(p);
-  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T *)p;
-  return SCO_OK;
-}
-
 int big_upload(const BigHost &bh, int batch, std::vector<void *> &allocs, BigDev &bd) {
   int rc;
-  if ((rc = upb(allocs, bh.row_elim, &bd.row_elim))) return rc;
-  if ((rc = upb(allocs, bh.row_epos, &bd.row_epos))) return rc;
-  if ((rc = upb(allocs, bh.er_ptr, &bd.er_ptr))) return rc;
-  if ((rc = upb(allocs, bh.er_row, &bd.er_row))) return rc;
-  if ((rc = upb(allocs, bh.free_rows, &bd.free_rows))) return rc;
-  if ((rc = upb(allocs, bh.pc_ptr, &bd.pc_ptr))) return rc;
-  if ((rc = upb(allocs, bh.pc_pos, &bd.pc_pos))) return rc;
-  if ((rc = upb(allocs, bh.pc_core, &bd.pc_core))) return rc;
+  if ((rc = sco_upload(allocs, bh.row_elim, &bd.row_elim))) return rc;
+  if ((rc = sco_upload(allocs, bh.row_epos, &bd.row_epos))) return rc;
+  if ((rc = sco_upload(allocs, bh.er_ptr, &bd.er_ptr))) return rc;
+  if ((rc = sco_upload(allocs, bh.er_row, &bd.er_row))) return rc;
+  if ((rc = sco_upload(allocs, bh.free_rows, &bd.free_rows))) return rc;
+  if ((rc = sco_upload(allocs, bh.pc_ptr, &bd.pc_ptr))) return rc;
+  if ((rc = sco_upload(allocs, bh.pc_pos, &bd.pc_pos))) return rc;
+  if ((rc = sco_upload(allocs, bh.pc_core, &bd.pc_core))) return rc;
   void *p = nullptr;
   SCO_HIP(hipMalloc(&p, (size_t)batch * bh.ws_doubles * sizeof(double)));
   SCO_HIP(hipMemset(p, 0, (size_t)batch * bh.ws_doubles * sizeof(double)));
@@ -1661,9 +1650,9 @@ extern "C" int sco_debug_stamps_bt(double *out) {      // diagnostic build only
 #endif
 int bt_upload(const BtHost &th, int batch, std::vector<void *> &allocs, BtDev &td) {
   int rc;
-  if ((rc = upb(allocs, th.ch_desc, &td.ch_desc))) return rc;
-  if ((rc = upb(allocs, th.it, &td.it))) return rc;
-  if ((rc = upb(allocs, th.cent, &td.cent))) return rc;
+  if ((rc = sco_upload(allocs, th.ch_desc, &td.ch_desc))) return rc;
+  if ((rc = sco_upload(allocs, th.it, &td.it))) return rc;
+  if ((rc = sco_upload(allocs, th.cent, &td.cent))) return rc;
   void *p = nullptr;
   SCO_HIP(hipMalloc(&p, (size_t)batch * th.blk_doubles * sizeof(double)));
   allocs.push_back(p);
@@ -1684,24 +1673,17 @@ int bt_upload(const BtHost &th, int batch, std::vector<void *> &allocs, BtDev &t
   td.ccon = (double *)p;
   td.mf_id = td.mf_h0 = td.mf_h1 = nullptr;
   if (th.use_mfma) {
-    if ((rc = upb(allocs, th.mf_id, &td.mf_id))) return rc;
-    if ((rc = upb(allocs, th.mf_h0, &td.mf_h0))) return rc;
-    if ((rc = upb(allocs, th.mf_h1, &td.mf_h1))) return rc;
+    if ((rc = sco_upload(allocs, th.mf_id, &td.mf_id))) return rc;
+    if ((rc = sco_upload(allocs, th.mf_h0, &td.mf_h0))) return rc;
+    if ((rc = sco_upload(allocs, th.mf_h1, &td.mf_h1))) return rc;
   }
   return SCO_OK;
 }
 
 template <int BS>
 static int bt_launch_bs(const BigArgs &bs, const BigArgs &ba, int batch, size_t lds, hipStream_t st, hipEvent_t ev_mid, hipEvent_t mid2) {
-  // hipFuncSetAttribute applies to the current device only
   static bool attr_done[64] = {};
-  int dev_ = 0;
-  (void)hipGetDevice(&dev_);
-  dev_ &= 63;
-  if (!attr_done[dev_]) {
-    SCO_HIP(hipFuncSetAttribute((const void *)qp_admm_bt_kernel<BS>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-    attr_done[dev_] = true;
-  }
+  SCO_LDS_ATTR((qp_admm_bt_kernel<BS>), 159 * 1024, attr_done);
   hipLaunchKernelGGL(qp_bt_factor_kernel<BS>, dim3(batch), dim3(256), 0, st, bs);
   SCO_HIP(hipGetLastError());
   if (ev_mid) SCO_HIP(hipEventRecord(ev_mid, st));

@@ -15,6 +15,8 @@ TIERS = (("default", {}), ("no row-local", dict(SCO_QP_NO_RL="1")), ("no row-loc
          ("no elimination", dict(SCO_QP_NO_ELIM="1")))
 import ctypes as C
 lib = L.load()
+# (tiers: the mask of sco_debug_qp_tiers -- bit 0 / 1 / 2 = the handle RUNS the row-local / register-offset / sliced-ELL kernel,
+# at most one of them, none = the generic kernel; 3 global memory, 4 its structured form, 5 wavefront tier, 6 MFMA setup)
 lib.sco_debug_qp_tiers.restype = C.c_int; lib.sco_debug_qp_tiers.argtypes = [C.c_void_p]
 
 for i in (43, 57):

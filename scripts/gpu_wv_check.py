@@ -10,6 +10,8 @@ from sco_py_amd import _lib as L
 
 os.environ["SCO_WV_MIN_PER_CU"] = "0"     # every launch on the wavefront tier (default: > 3.3 problems per CU)
 lib = L.load()
+# (tiers printed below: sco_debug_qp_tiers -- bits 0 / 1 / 2 = the ONE on-chip kernel the handle runs, row-local / register-offset /
+# sliced-ELL; 3 global memory, 4 its structured form, 5 wavefront tier, 6 MFMA setup)
 lib.sco_debug_qp_tiers.restype = C.c_int; lib.sco_debug_qp_tiers.argtypes = [C.c_void_p]
 
 
