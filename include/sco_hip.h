@@ -431,6 +431,14 @@ int sco_sqp_last_tiers(const sco_sqp *h, double ms[2], long long iters[2], int l
 int sco_debug_sqp_mixed(const sco_sqp *h, int out[2]);
 int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu);
 
+/* The G-resident sweep of the wavefront tier (diagnostics; host arithmetic, no GPU needed; csrc/sco_admm_wv.hip:
+ * wv_gres_slot).  Block position `pos` of the kernel with `nstep` block steps per chain (0 .. nstep-1 chain A, nstep the
+ * middle block, nstep+1 .. 2 nstep chain B) -> out = {DPP row pair (0: rows 0 and 1, 1: rows 2 and 3), row of the pair
+ * (= chain; 0 for the middle block, which both rows of pair 1 compute), register slot (the middle block: (nstep + 1) / 2),
+ * index of component 0 of its r / x~ inside a block vector, index of its couplings}; all -1 for a position no sweep lane
+ * holds. */
+int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]);
+
 /* The schedule of the SQP round loop on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/sqp_sched.h).  The
  * SCO_SQP_* environment variables are read as by sco_sqp_solve.
  * sco_debug_sqp_schedule: in = {batch, cus, admm_slice, adaptive_rho, max_iter, adaptive rho interval, max_qp_solves,

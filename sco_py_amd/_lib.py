@@ -99,6 +99,7 @@ ABI = {
     "sco_sqp_last_tiers": (C.c_int, [C.c_void_p, _DP, _LP, _IP]),
     "sco_debug_sqp_mixed": (C.c_int, [C.c_void_p, _IP]),
     "sco_debug_mix_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sco_debug_wv_gres_slot": (C.c_int, [C.c_int, C.c_int, _IP]),
     "sco_debug_sqp_schedule": (C.c_int, [_IP, _IP, _IP, _IP]),
     "sco_debug_stage_sweep": (C.c_int, [C.c_int, _DP, _DP, _IP, _DP]),
     "sco_debug_qp_launch_plan": (C.c_int, [_IP, _DP, _IP]),

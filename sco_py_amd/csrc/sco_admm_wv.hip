@@ -56,6 +56,9 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #ifndef WV_VARIANT
 #define WV_VARIANT 0          // timing variants (scripts/build_ablate.py wv:WV_VARIANT=1): 1 = plain v_fmac_f64 instead of the DPP broadcasts (results wrong)
 #endif
+#ifndef WV_GRES
+#define WV_GRES 1             // 0 = every instantiation on the LDS-fed sweep (scripts/build_ablate.py wv:WV_GRES=0)
+#endif
 #if WV_VARIANT == 1
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
 #endif
@@ -72,6 +75,32 @@ __host__ __device__ __forceinline__ size_t wv_tri(int i, int j) { return (size_t
 //                                    the blocks of chain B (both chains read their piece j in the same instruction)
 __host__ __device__ inline int wv_vidx(int npos, int pos, int k) { return (k >> 1) * 2 * npos + 2 * pos + (k & 1); }
 __host__ __device__ inline int wv_gidx(int nstep, int pos, int i, int c) { return 64 * pos + 16 * (((c >> 1) + (pos > nstep ? 1 : 0)) & 3) + 2 * i + (c & 1); }
+
+// The G-resident sweep (WV_GRES, qp_admm_wv_kernel) runs a chain on TWO DPP rows: with HS = (NSTEP + 1) / 2, rows 0 and 1
+// (pair 0) take the first HS positions of chains A and B, rows 2 and 3 (pair 1) the rest and the middle block, every lane
+// with its rows of G in registers: slot s of a lane is the s-th position of its half, the middle block sits in slot HS of
+// pair 1 (both of its rows compute it, row 2 stores it).  Block position -> (row pair, row of the pair = chain, register
+// slot, index of component 0 of its r / x~ inside a block vector, index of its couplings inside ef / en).
+struct WvGresSlot { int pair, row, slot, vidx, eidx; };
+__host__ __device__ inline WvGresSlot wv_gres_slot(int nstep, int pos) {
+  const int hs = (nstep + 1) / 2, npos = 2 * nstep + 2;
+  WvGresSlot s = {-1, -1, -1, -1, -1};
+  if (pos < 0 || pos > 2 * nstep) return s;                       // (2 nstep + 1: the dummy block of idle lanes, no sweep lane)
+  if (pos == nstep) { s.pair = 1; s.row = 0; s.slot = hs; }
+  else {
+    const int chain = pos > nstep ? 1 : 0, st = pos - (chain ? nstep + 1 : 0);
+    s.pair = st >= hs ? 1 : 0; s.row = chain; s.slot = st - (s.pair ? hs : 0);
+  }
+  s.vidx = wv_vidx(npos, pos, 0); s.eidx = pos * 8;
+  return s;
+}
+// out[5] = pair, row, slot, vidx, eidx of block position pos in the NSTEP-step kernel (-1s: no sweep lane holds it)
+extern "C" int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]) {
+  if (!out || nstep <= 0) return SCO_ERR_ARG;
+  const WvGresSlot s = wv_gres_slot(nstep, pos);
+  out[0] = s.pair; out[1] = s.row; out[2] = s.slot; out[3] = s.vidx; out[4] = s.eidx;
+  return SCO_OK;
+}
 
 // int tables, [..][64] lane-minor; offsets in units of 64 ints
 struct WvTab {
@@ -474,9 +503,24 @@ __device__ __forceinline__ const T *wv_opaque(const T *p) { asm volatile("" : "+
 // OSQP's estimate (osqp_rho_estimate, sco_admm_check.h) from norms that ride along in that test, and when rho must change it
 // parks the solve like a used-up slice.  The setup and factor kernels then run for the problem again (smask) and the next
 // launch resumes it: the right-hand side is rebuilt from x, z, y on every resume, so the new rho needs nothing further.
+//
+// GRES: the G-resident sweep (wv_gres_slot).  G is a constant of the QP; the LDS-fed sweep streams it through LDS every
+// iteration, 16 lanes wide, and is bound by that.  Here every sweep lane keeps its rows of G in registers over
+// the plain iterations (read again from the LDS image behind every termination test): HS + 1 blocks of registers instead of
+// the ring, the kept blocks and the NSTEP intermediate vectors of the LDS-fed form, and no LDS read of G in the iteration
+// loop.  The arithmetic of every block step is the LDS-fed sweep's, instruction for instruction, on the same values: the
+// results are bit-identical.  An instantiation takes this form where it fits without scratch and without more accumulation
+// registers than the LDS-fed form (wv_gres_fits, from the compiler's resource report: profiles/wv_gres.md).
+constexpr bool wv_gres_fits(int BS, int NS, int NV, int NSTEP, int LPB, int EXT) {
+  // (the 7-wide adaptive-rho instantiations stay on the LDS-fed sweep: <7,4,3,10,0,3> would take 246 accumulation registers
+  // against 244, <7,4,3,10,3,3> is at 256 + 256 either way)
+  return WV_GRES != 0 && NSTEP % 2 == 0 && !(BS == 7 && (EXT & 2));
+}
 template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
 __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr bool ADAPT = (EXT & 2) != 0;
+  constexpr bool GRES = wv_gres_fits(BS, NS, NV, NSTEP, LPB, EXT);
+  constexpr int HS = (NSTEP + 1) / 2, H2 = NSTEP - HS;
   const int g = blockIdx.x, lane = threadIdx.x;
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
   if (b < 0 || (a.active && !a.active[b])) return;
@@ -600,16 +644,28 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   const double x_rho = x_row >= 0 ? a.rhov[(size_t)b * m + x_row] : 1.0, x_rinv = 1.0 / x_rho, x_w = x_row >= 0 ? (double)a.w[(size_t)b * m + x_row] : 0.0;
   double x_z = x_row >= 0 && resume ? szg[x_row] : 0.0, x_y = x_row >= 0 && resume ? syg[x_row] : 0.0;
   // sweep roles: DPP row 0 (and its copy, row 2) runs chain A, row 1 (and 3) chain B; lane k of a row holds component k
-  const int srow = lane >> 4, k8 = lane & 7, chain = srow & 1;
-  const bool sw_store = srow < 2 && (lane & 15) < 8;
-  const int pos0 = chain ? NSTEP + 1 : 0;
+  // (GRES: rows 0 and 1 hold the first HS positions of the two chains, rows 2 and 3 the rest: pos0 is slot 0 of the lane)
+  const int srow = lane >> 4, k8 = lane & 7, chain = srow & 1, half = GRES ? srow >> 1 : 0;
+  const bool sw_store = (GRES || srow < 2) && (lane & 15) < 8;
+  const int pos0 = (chain ? NSTEP + 1 : 0) + half * HS;
+  const WvGresSlot sl0 = wv_gres_slot(NSTEP, pos0);                                    // (the next block: + 2 in a vector, + 8 in the couplings)
   const double *const sw_g = lds + oG + pos0 * 64 + k8 * 2 + (chain ? 16 : 0);        // row k8 of the chain's first block, piece 0
   const double *const sw_gd = lds + oG + pos0 * 64 + k8 * 2 + (chain ? 0 : 48);       // ... its piece 3
-  double *const sw_v = lds + oR + wv_vidx(NPOS, pos0, k8);                              // r of the chain's first block (next block: + 2)
-  const double *const sw_e = lds + oEF + pos0 * 8 + k8;                                // couplings of the chain's first block
+  double *const sw_v = lds + oR + sl0.vidx + wv_vidx(NPOS, 0, k8);                      // r of the chain's first block (next block: + 2)
+  const double *const sw_e = lds + oEF + sl0.eidx + k8;                                // couplings of the chain's first block
   const double *const md_g = lds + oG + NSTEP * 64 + k8 * 2;
   double *const md_v = lds + oR + wv_vidx(NPOS, NSTEP, k8);
   const double *const md_e = lds + oEF + NSTEP * 8 + k8;
+  // GRES: the lane's rows of G, read from the LDS image in front of every run of plain iterations, i.e. once per termination
+  // test: held across the test as well, they would sit on top of its peak of live registers (the certificates' delta
+  // vectors, the scalings) and push the kernel into scratch.  24 reads per `check` iterations instead of 39 per iteration.
+  WvRow<BS> gr[GRES ? HS : 1], gmd;
+  auto load_g = [&]() {
+    static_assert(!GRES || H2 == HS, "the second half recomputes the first on its idle rows: both halves need the same step count");
+#pragma unroll
+    for (int s = 0; s < HS; s++) gr[s] = wv_row<BS>(sw_g + s * 64, sw_gd + s * 64);
+    gmd = wv_row<BS>(md_g, md_g + 48);
+  };
   WV_SYNC();
 
   // accumulators of the termination test that ride along in the checked step
@@ -766,7 +822,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
 
   // x~_C = S^-1 r by the twisted block factorisation: forward sweeps of both chains, the middle block, backward sweeps.
   // Nothing is stored inside the sweeps: the NSTEP intermediate vectors of a chain stay in registers.
-  auto sweep = [&]() {
+  auto sweep_lds = [&]() {
     // only the 16 lanes that hold a component of one of the two chains take part: the others would fetch the same rows of
     // G again (four wavefronts share a CU's LDS pipe).
     // A block step is ~60 cycles of arithmetic (seven dependent v_fmac_f64_dpp in two chains, one fma, one add) and an LDS
@@ -843,6 +899,84 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     }
     WV_SYNC();
   };
+  // The same sweeps with G resident (GRES).  A block step is issued once for the whole wavefront, NSTEP of them per pass as
+  // before; slot s of a lane is position s of its half.  Forward: HS steps, live on rows 0 and 1; one v_permlane32_swap per
+  // register half hands the last vector up to rows 2 and 3; HS steps on the same slots, live on rows 2 and 3; the middle
+  // block between rows 2 and 3.  Backward: the reverse, with one hand-back.  The idle row pair of a half needs no
+  // predication: rows 0 and 1 restart the second forward half from 0 as they started the first, and rows 2 and 3 restart
+  // the second backward half from the middle block's x~, so each pair computes its own values again, on the same inputs with
+  // the same instructions, while the other pair does its work (what rows 2 and 3 leave behind in the first forward half,
+  // and rows 0 and 1 in the first backward half, is overwritten).  Right-hand sides and couplings come from LDS through
+  // the lane's own addresses, 8 bytes per lane and step, asked for WV_PD steps ahead; all 64 lanes run the arithmetic
+  // (lanes 8 .. 15 of a row mirror lanes 0 .. 7), the sweep lanes store.
+  auto sweep_res = [&]() {
+    constexpr int PD = WV_PD < NSTEP ? WV_PD : NSTEP;
+    double vs[HS], xs[HS], rq[PD], eq[PD], eb[PD];
+    auto fetch_fwd = [&](int i, double &r, double &e) {          // issue step i of the forward pass; i = NSTEP: the middle block
+      if (i < NSTEP) { const int s = i < HS ? i : i - HS; r = sw_v[s * 2]; e = sw_e[s * 8]; }
+      else if (i == NSTEP) { r = md_v[0]; e = md_e[0]; }
+    };
+    auto bslot = [&](int j) { return j < H2 ? H2 - 1 - j : NSTEP - 1 - j; };      // slot of issue step j of the backward pass
+    auto fetch_bwd = [&](int j, double &e) { if (j < NSTEP) e = sw_e[bslot(j) * 8 + (oEN - oEF)]; };
+#pragma unroll
+    for (int i = 0; i < PD; i++) fetch_fwd(i, rq[i], eq[i]);
+    double vprev = 0.0;
+#pragma unroll
+    for (int i = 0; i < NSTEP; i++) {
+      if (i == HS) {
+        // .x: every lane holds the value of its lane in the LOWER half; rows 0 and 1 start again from 0
+        const wv_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(vprev), (unsigned)__double2loint(vprev), false, false);
+        const wv_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(vprev), (unsigned)__double2hiint(vprev), false, false);
+        vprev = half ? __hiloint2double((int)hi.x, (int)lo.x) : 0.0;
+      }
+      const int s = i < HS ? i : i - HS;
+      const double rr = rq[i % PD], ee = eq[i % PD];
+      fetch_fwd(i + PD, rq[i % PD], eq[i % PD]);
+      const double w = __builtin_fma(-ee, vprev, rr);
+      vprev = wv_matvec<BS>(0.0, w, gr[s]);
+      vs[s] = vprev;
+    }
+    const double emk = lds[oEM + k8], vlast = vprev;
+    // the middle block needs the last vector of both chains: row 2 holds chain A's, row 3 chain B's
+    double vother;
+    {
+      const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(vlast), (unsigned)__double2loint(vlast), false, false);
+      const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(vlast), (unsigned)__double2hiint(vlast), false, false);
+      // .x: odd rows now hold the even rows' values; .y: even rows now hold the odd rows' values
+      vother = chain ? __hiloint2double((int)hi.x, (int)lo.x) : __hiloint2double((int)hi.y, (int)lo.y);
+    }
+    // (slot NSTEP % PD of the ring holds the middle block's right-hand side and coupling)
+    const double rm = rq[NSTEP % PD], em_ = eq[NSTEP % PD];
+    const double vA = chain ? vother : vlast, vB = chain ? vlast : vother;
+#pragma unroll
+    for (int j = 0; j < PD; j++) fetch_bwd(j, eb[j]);
+    double w = __builtin_fma(-em_, vA, rm);
+    w = __builtin_fma(-emk, vB, w);
+    double xn = wv_matvec<BS>(0.0, w, gmd);
+    const double xmid = xn;
+#pragma unroll
+    for (int j = 0; j < NSTEP; j++) {
+      if (j == H2) {
+        // .y: every lane holds the value of its lane in the UPPER half; rows 2 and 3 start again from the middle block
+        const wv_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(xn), (unsigned)__double2loint(xn), false, false);
+        const wv_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(xn), (unsigned)__double2hiint(xn), false, false);
+        xn = half ? xmid : __hiloint2double((int)hi.y, (int)lo.y);
+      }
+      const int s = bslot(j);
+      const double ee = eb[j % PD];
+      fetch_bwd(j + PD, eb[j % PD]);
+      const double u = -(ee * xn);
+      xn = wv_matvec<BS>(vs[s], u, gr[s]);
+      xs[s] = xn;
+    }
+    if (sw_store) {
+#pragma unroll
+      for (int s = 0; s < HS; s++) sw_v[s * 2 + (oXT - oR)] = xs[s];
+      if (srow == 2) md_v[oXT - oR] = xmid;
+    }
+    WV_SYNC();
+  };
+  auto sweep = [&]() { if constexpr (GRES) sweep_res(); else sweep_lds(); };
 
   if ((EXT & 1) && a.warm && !resume) {
     // OSQP-style warm start from the previous solution of this handle (x, y unscaled in a.x / a.y), the formulas of the
@@ -895,6 +1029,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   const int stop = (a.slice > 0 && it0 + a.slice < a.max_iter) ? it0 + a.slice : a.max_iter;
   while (!status && iter < stop && !(ADAPT && rho_new > 0.0)) {
     int next = stop;
+    if constexpr (GRES) load_g();
     if (a.check > 0) { next = (iter / a.check + 1) * a.check; if (next > stop) next = stop; }
     while (iter + 2 < next) { iter++; if (!(ablate & 1)) sweep(); if (!(ablate & 2)) rows(std::integral_constant<int, 1>{}); }
     if (iter + 1 < next) { iter++; if (!(ablate & 1)) sweep(); if (!(ablate & 2)) rows(std::integral_constant<int, 1>{}); }

@@ -10,8 +10,8 @@ sys.path.insert(0, ROOT)
 from sco_py_amd import _build
 
 # arguments: ablation masks as integers; "vN" = -DRL_VARIANT=N; "name=path.hip" = an alternative kernel source;
-# "wv:NAME[=VAL][,NAME=VAL]" = the wavefront tier's source (sco_admm_wv.hip) with those defines (WV_PD, WV_VARIANT; WV_ABLATE:
-# the kernel that honours SCO_WV_ABLATE, for scripts/gpu_wv_time.py);
+# "wv:NAME[=VAL][,NAME=VAL]" = the wavefront tier's source (sco_admm_wv.hip) with those defines (WV_PD, WV_VARIANT; WV_GRES=0: every instantiation
+# on the LDS-fed sweep; WV_ABLATE: the kernel that honours SCO_WV_ABLATE, for scripts/gpu_wv_time.py);
 # "wvfile:TAG=path.hip" = an alternative source file in its place
 masks = sys.argv[1:] or ["0", "1", "2", "4", "8", "12", "16", "31"]
 _build.build()                                   # product objects are current
