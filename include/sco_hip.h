@@ -240,7 +240,10 @@ void sco_sqp_default_params(sco_sqp_params *p);
 #define SCO_FAM_FLAG_VEL_LIMITS 16 /* OR-ed into `family`: joint-velocity limits
                                   |theta[t+1][j] - theta[t][j]| <= vmax as LINEAR inequality rows
                                   (LEqExpr on an AffExpr: they go straight into every QP, the projection
-                                  QP included, prob.py:126-131, 317-346); vmax via sco_sqp_load_vel_limit */
+                                  QP included, prob.py:126-131, 317-346); vmax via sco_sqp_load_vel_limit.
+                                  The QP handle plans them as link rows of the wavefront ADMM tier (two per
+                                  joint and transition): rounds run there by the rule of the family without
+                                  them (SCO_WV_MIN_PER_CU), with adaptive rho on the row-local kernel */
 #define SCO_FAM_FLAG_JOINT_LIMITS 32 /* OR-ed into `family`: joint limits lo_j <= theta[t][j] <= hi_j at every
                                   timestep as two more LINEAR inequality blocks (theta <= hi, then -theta <= -lo,
                                   after the velocity rows); lo, hi via sco_sqp_load_joint_limits */
@@ -455,7 +458,8 @@ int sco_debug_stage_sweep(int n, const double *begin_ms, const double *end_ms, c
 
 /* What a launch on a QP handle does, on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/qp_tier.h).
  * sco_debug_qp_launch_plan: in[24] = {on-chip kernel of the handle (0 row-local, 1 register-offset, 2 sliced-ELL, 3 generic),
- * global-memory tier, its structured form, wavefront tier, Cholesky cross-check (0 / 1 each), batch, order of the core, CUs,
+ * global-memory tier, its structured form, wavefront tier (2: its plan holds link rows), Cholesky cross-check (0 / 1 each),
+ * batch, order of the core, CUs,
  * adaptive_rho, adaptive_rho_interval, check_termination, max_iter, slice asked for, setup mask (0 an array, 1 all, 2 none),
  * fewest problems of a wavefront launch (< 0: from the CUs and SCO_WV_MIN_PER_CU, as a launch does), then the launch window:
  * given (0 / 1), b0, nb, tier, index list given, side_b0, side_nb, side_slices, side stream and its three events given};

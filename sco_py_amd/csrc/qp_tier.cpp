@@ -22,6 +22,8 @@ QpCreateEnv qp_create_env() {
 // still alive (no round selection), a solve parks at every rho change and the launches are short and mostly narrow.  Measured
 // on `bench.py --beyond` (1024 problems, 4 per CU, 122 launches of ~100 iterations per step): 503 ms of ADMM launches per
 // step on this tier against 285 ms on the row-local kernel (profiles/wv_extensions.md).  The variable still applies when set.
+// A plan with link rows (velocity limits) goes by the same rule as a link-free one: on the 1024-problem 7x20 step every run on
+// this tier was faster than every run on the row-local kernel (profiles/wv_link_rows.md).
 int sco_wv_min_live(int cus, bool adaptive) {
   const char *e = getenv("SCO_WV_MIN_PER_CU");
   if (!e && adaptive) return INT_MAX;
@@ -93,7 +95,8 @@ QpLaunchPlan qp_launch_plan(const QpLaunchIn &in) {
         !at_end || in.side_slices <= 0 || !in.side_ready)
       return plan_error(p, SCO_ERR_STATE, QP_ERR_MIXED);
   }
-  p.wv_now = in.use_wv && (in.window && in.tier ? in.tier >= 2 : p.nwg >= in.wv_min);
+  // (link rows have no adaptive-rho instantiation on that tier: such launches stay on the row-local kernel)
+  p.wv_now = in.use_wv && !(adaptive && in.wv_links) && (in.window && in.tier ? in.tier >= 2 : p.nwg >= in.wv_min);
   p.rho_init = adaptive && in.mask != QP_MASK_NONE;
   p.route = in.use_big ? (in.use_bt ? QP_ROUTE_BIG_BT : QP_ROUTE_BIG_DENSE) : QP_ROUTE_ONCHIP;
   if (p.route != QP_ROUTE_ONCHIP) { p.wv_now = false; return p; }
@@ -115,7 +118,7 @@ QpLaunchPlan qp_launch_plan(const QpLaunchIn &in) {
 extern "C" int sco_debug_qp_launch_plan(const int *in, const double *tol, int *out) {
   if (!in || !tol || !out) return -1;
   QpLaunchIn li;
-  li.kern = in[0]; li.use_big = in[1] != 0; li.use_bt = in[2] != 0; li.use_wv = in[3] != 0; li.factor_cholesky = in[4] != 0;
+  li.kern = in[0]; li.use_big = in[1] != 0; li.use_bt = in[2] != 0; li.use_wv = in[3] != 0; li.wv_links = in[3] == 2; li.factor_cholesky = in[4] != 0;
   li.batch = in[5]; li.n_c = in[6]; li.cus = in[7];
   li.adaptive_rho = in[8]; li.adaptive_rho_interval = in[9]; li.check_termination = in[10]; li.max_iter = in[11];
   li.adaptive_rho_tolerance = *tol;

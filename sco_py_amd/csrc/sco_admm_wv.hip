@@ -16,9 +16,11 @@
 //     rows in lane-private LDS; partial column sums and the sweep's vectors go through 10 KB of LDS; no barrier ever
 //     waits for another wavefront.  A problem needs <= 40 KB of LDS and one wavefront: 4 problems per CU.
 //
-// The tier takes patterns with this structure only (wv_plan_build), and per problem only VALUES with the structure of a
-// penalty QP (hinge rows l = -inf with one common weight, slack rows [0, inf), everything on the base rho: checked by
-// qp_wv_factor_kernel).  A problem that fails the value test is left to the row-local kernel, which the launcher runs
+// The tier takes patterns with this structure only (wv_plan_build): hinge rows inside one timestep with their slack and its
+// bound row, at most two single rows per core variable, and LINK rows -- no slack, the same in-block index of two
+// neighbouring timesteps, at most WV_NL per pair (velocity limits; the LNK instantiations of the kernel, fixed rho only).
+// Per problem it takes only VALUES with the structure of a penalty QP (hinge rows l = -inf with one common weight, slack
+// rows [0, inf), everything on the base rho, link rows with weight 1: checked by qp_wv_factor_kernel).  A problem that fails the value test is left to the row-local kernel, which the launcher runs
 // right behind this one for exactly those problems -- so the tier never changes what is solved, only where.
 //
 // Block positions.  The sweeps are unrolled NSTEP times (a template argument); both chains are padded AT THEIR START
@@ -105,8 +107,12 @@ extern "C" int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]) {
 // int tables, [..][64] lane-minor; offsets in units of 64 ints
 struct WvTab {
   int pos, hrow, hbrow, hevar, heidx, hepos, hbpos, hjpos, vvar, vrow, vpos, vpk, vpkm, vpkp, vpd, vpm, vpp, xrow, xpos, xpk, total;
+  int lrow, lplo, lphi;           // link slots, NV x NL each, behind everything else (NL = 0: none, `total` as without them)
 };
-__host__ __device__ inline WvTab wv_tab_layout(int NS, int NV) {
+// link slot s of variable slot v (the variable is the row's end in block t, its partner the same in-block index of block
+// t + 1): lrow the row, lplo / lphi the CSC positions of A(row, own) and A(row, partner); the partner's place in a block
+// vector is the slot's vpkp
+__host__ __device__ inline WvTab wv_tab_layout(int NS, int NV, int NL = 0) {
   WvTab t; int o = 0;
   t.pos = o; o += 1;
   t.hrow = o; o += NS; t.hbrow = o; o += NS; t.hevar = o; o += NS; t.heidx = o; o += NS; t.hepos = o; o += NS; t.hbpos = o; o += NS;
@@ -114,6 +120,7 @@ __host__ __device__ inline WvTab wv_tab_layout(int NS, int NV) {
   t.vvar = o; o += NV; t.vrow = o; o += NV; t.vpos = o; o += NV; t.vpk = o; o += NV; t.vpkm = o; o += NV; t.vpkp = o; o += NV;
   t.vpd = o; o += NV * 8; t.vpm = o; o += NV; t.vpp = o; o += NV;
   t.xrow = o; o += 1; t.xpos = o; o += 1; t.xpk = o; o += 1;
+  t.lrow = o; o += NV * NL; t.lplo = o; o += NV * NL; t.lphi = o; o += NV * NL;
   t.total = o;
   return t;
 }
@@ -125,14 +132,51 @@ __host__ __device__ inline WvTab wv_tab_layout(int NS, int NV) {
 __host__ __device__ inline int wv_cst_h(int q) { return 3 * q; }
 __host__ __device__ inline int wv_cst_v(int NS, int v) { return 3 * NS + 13 * v; }
 __host__ __device__ inline int wv_cst_x(int NS, int NV) { return 3 * NS + 13 * NV; }
+// link slot i = v NL + s: 1/E of its row (plans with link rows only)
+__host__ __device__ inline int wv_cst_l(int NS, int NV, int i) { return 3 * NS + 13 * NV + 1 + i; }
+// The four constants of a link slot (its two A entries, l, u) live in registers where the instantiation has room for them,
+// else lane-private in LDS, by the compiler's resource report (profiles/wv_link_rows.md): the 7-wide instantiations hold
+// 256 + ~200 registers without link rows and would spill with 48 more.  In LDS they take the place of the constants of the
+// termination test (qp_admm_wv_kernel, CKG), so that the plan stays within 40 KB.
+__host__ __device__ constexpr bool wv_link_regs(int BS) { return BS != 7; }
 // (v_rcp_f64, one instruction: these reciprocals only scale the norms of the infeasibility tests)
 __device__ __forceinline__ double wv_recip(double x) { return x != 0.0 ? __builtin_amdgcn_rcp(x) : 0.0; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host plan
 // ---------------------------------------------------------------------------------------------------------------------
-bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
+// Why a pattern without a block structure has none, for the refusal's reason only: the block order is read off P (the
+// smoothing objective couples c with c + bs) and the rows without a slack are judged by it.
+static int wv_why_no_blocks(const QpPlan &pl) {
+  int bs = 0;
+  for (int c = 0; c < pl.n; c++)
+    for (int t = pl.Pp[c]; t < pl.Pp[c + 1]; t++) {
+      const int r = pl.Pi[t];
+      if (r != c && pl.core_of[r] >= 0 && pl.core_of[c] >= 0) bs = std::max(bs, std::abs(pl.core_of[c] - pl.core_of[r]));
+    }
+  if (bs <= 0 || pl.n_c % bs) return WV_WHY_OTHER;
+  int why = WV_WHY_OTHER;
+  for (int i = 0; i < pl.m; i++) {
+    int nc = 0, c0 = -1, c1 = -1; bool slack = false;
+    for (int s = pl.Rp[i]; s < pl.Rp[i + 1]; s++) {
+      const int j = pl.Rj[s];
+      if (pl.elim_of[j] >= 0) { slack = true; continue; }
+      const int c = pl.core_of[j];
+      if (!nc) c0 = c1 = c; else { c0 = std::min(c0, c); c1 = std::max(c1, c); }
+      nc++;
+    }
+    if (slack || nc < 2) continue;
+    if (nc >= 3) return WV_WHY_THREE_CORE;
+    if (c1 / bs == c0 / bs) why = WV_WHY_SAME_BLOCK;
+    else if (c1 % bs != c0 % bs) why = WV_WHY_INDEX;
+    else if (c1 / bs > c0 / bs + 1) why = WV_WHY_FAR_BLOCKS;
+  }
+  return why;
+}
+
+bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
   wh = WvHost();
+  wh.why = WV_WHY_OTHER;
   const int n_c = pl.n_c, n_e = pl.n_e, m = pl.m;
   if (n_e <= 0 || n_c <= 0) return false;
   // ---- block structure of S: within a block, or between neighbouring blocks at equal in-block index
@@ -147,24 +191,39 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
     return true;
   };
   int bs = 0;
-  if (valid(hb)) bs = hb; else if (valid(n_c)) bs = n_c; else return false;
+  if (valid(hb)) bs = hb; else if (valid(n_c)) bs = n_c; else { wh.why = wv_why_no_blocks(pl); return false; }
   const int nb = n_c / bs;
   for (int e = 0; e < n_e; e++) if (pl.Pdiag[pl.elim_var[e]] >= 0) return false;      // no P entry on an eliminated variable
   // ---- rows
   std::vector<int> h_of(n_e, -1), b_of(n_e, -1), hblk(n_e, -1);
-  std::vector<std::vector<int>> single(n_c);
+  std::vector<std::vector<int>> single(n_c), link(n_c);       // link[c]: the rows on c and c + bs, in row order
   for (int i = 0; i < m; i++) {
-    int ne = 0, nc = 0, e = -1, blk = -1; bool one_blk = true;
+    int ne = 0, nc = 0, e = -1, blk = -1, c0 = -1, c1 = -1; bool one_blk = true;
     for (int s = pl.Rp[i]; s < pl.Rp[i + 1]; s++) {
       const int j = pl.Rj[s];
       if (pl.elim_of[j] >= 0) { ne++; e = pl.elim_of[j]; }
-      else { const int t = pl.core_of[j] / bs; if (nc && t != blk) one_blk = false; blk = t; nc++; }
+      else {
+        const int c = pl.core_of[j], t = c / bs;
+        if (nc && t != blk) one_blk = false;
+        if (!nc) c0 = c1 = c; else { c0 = std::min(c0, c); c1 = std::max(c1, c); }
+        blk = t; nc++;
+      }
     }
     if (ne == 1 && nc >= 1 && one_blk) { if (h_of[e] >= 0) return false; h_of[e] = i; hblk[e] = blk; }
     else if (ne == 1 && nc == 0) { if (b_of[e] >= 0) return false; b_of[e] = i; }
     else if (ne == 0 && nc == 1) single[pl.core_of[pl.Rj[pl.Rp[i]]]].push_back(i);
-    else return false;
+    else if (ne == 0 && nc == 2) {
+      // a link row: no slack, one in-block index of two neighbouring blocks; it belongs to the variable of the earlier block
+      if (one_blk) { wh.why = WV_WHY_SAME_BLOCK; return false; }
+      if (c1 % bs != c0 % bs) { wh.why = WV_WHY_INDEX; return false; }
+      if (c1 != c0 + bs) { wh.why = WV_WHY_FAR_BLOCKS; return false; }
+      if (!allow_links) { wh.why = WV_WHY_LINKS_OFF; return false; }
+      if ((int)link[c0].size() >= WV_NL) { wh.why = WV_WHY_THIRD_LINK; return false; }
+      link[c0].push_back(i); wh.n_link++;
+    }
+    else { if (ne == 0 && nc >= 3) wh.why = WV_WHY_THREE_CORE; return false; }
   }
+  wh.NL = wh.n_link > 0 ? WV_NL : 0;
   for (int e = 0; e < n_e; e++)
     if (h_of[e] < 0 || b_of[e] < 0 || pl.Ap[pl.elim_var[e] + 1] - pl.Ap[pl.elim_var[e]] != 2) return false;
   int n_extra = 0;
@@ -190,7 +249,7 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
   else if (NS <= 2 && NV <= 2 && mid <= 8) { wh.BS = 8; wh.NS = 2; wh.NV = 2; wh.NSTEP = 8; }
   else if (NS <= 2 && NV <= 2 && mid <= 10) { wh.BS = 8; wh.NS = 2; wh.NV = 2; wh.NSTEP = 10; }
   else if (bs == 7 && NS <= 4 && NV <= 3 && mid <= 10) { wh.BS = 7; wh.NS = 4; wh.NV = 3; wh.NSTEP = 10; }
-  else return false;
+  else { wh.why = WV_WHY_SHAPE; return false; }
   wh.bs = bs; wh.nb = nb; wh.mid = mid; wh.lpb = lpb; wh.n_extra = n_extra;
   const int NSTEP = wh.NSTEP, lenB = nb - 1 - mid, npos = 2 * NSTEP + 2, dummy = npos - 1;
   auto pos_of = [&](int t) { return t < mid ? NSTEP - mid + t : t == mid ? NSTEP : 2 * NSTEP + 1 - lenB + (nb - 1 - t); };
@@ -203,7 +262,7 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
     for (int t = pl.Pp[c]; t < pl.Pp[c + 1]; t++) if (pl.Pi[t] == r) return t;
     return -1;
   };
-  const WvTab T = wv_tab_layout(wh.NS, wh.NV);
+  const WvTab T = wv_tab_layout(wh.NS, wh.NV, wh.NL);
   wh.tab.assign((size_t)T.total * 64, -1);
   auto at = [&](int off, int lane) -> int & { return wh.tab[(size_t)off * 64 + lane]; };
   for (int l = 0; l < 64; l++) {
@@ -234,6 +293,10 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
       at(T.vpm + v, l) = t > 0 ? ppos(var, pl.core_var[(t - 1) * bs + k]) : -1;
       at(T.vpp + v, l) = t + 1 < nb ? ppos(var, pl.core_var[(t + 1) * bs + k]) : -1;
       if (single[c].size() == 2) { at(T.xrow, xl) = single[c][0]; at(T.xpos, xl) = apos(single[c][0], var); at(T.xpk, xl) = wv_vidx(npos, p, k); xl++; }
+      for (int s = 0; s < (int)link[c].size(); s++) {               // (link[c] is empty in the last block: c + bs does not exist)
+        const int i = v * wh.NL + s, row = link[c][s];
+        at(T.lrow + i, l) = row; at(T.lplo + i, l) = apos(row, var); at(T.lphi + i, l) = apos(row, pl.core_var[c + bs]);
+      }
     }
   }
   // LDS of the ADMM kernel (doubles): G, ef, en, em | r, x~, x, extra | Jacobian rows (unless they live in registers) | partials
@@ -241,10 +304,21 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh) {
   wh.g_doubles = (size_t)npos * 64 + 2 * (size_t)npos * 8 + 8;
   // (+ the constants of the termination test, lane-minor: 3 NS + 5 NV + 1 slots of 64 doubles)
   wh.lds_doubles = wh.g_doubles + 4 * (size_t)npos * 8 + (jreg ? 0 : (size_t)wh.NS * 512) + (size_t)npos * lpb * 8 + (size_t)(3 * wh.NS + 5 * wh.NV + 1) * 64;
-  wh.lds_bytes = wh.lds_doubles * sizeof(double);
   wh.cst_slots = 3 * wh.NS + 13 * wh.NV + 1;
+  if (wh.NL) {
+    // link rows: one more block vector (the partner's share of the right-hand side); where the instantiation keeps the
+    // slots' four constants in lane-private LDS, they take the place of the constants of the termination test
+    const int nl = wh.NV * wh.NL;
+    wh.lds_doubles += (size_t)npos * 8;
+    if (!wv_link_regs(wh.BS)) wh.lds_doubles = wh.lds_doubles - (size_t)(3 * wh.NS + 5 * wh.NV + 1) * 64 + (size_t)nl * 4 * 64;
+    wh.cst_slots += nl;
+  }
+  wh.lds_bytes = wh.lds_doubles * sizeof(double);
   // the tier pays only with FOUR problems per CU (one wavefront per SIMD): 40 KB each at most
-  return wh.lds_bytes <= 40 * 1024;
+  wh.per_cu = SCO_WV_PER_CU;
+  const bool fits = wh.lds_bytes <= 40 * 1024;
+  wh.why = fits ? WV_OK : WV_WHY_LDS;
+  return fits;
 }
 
 int wv_upload(const WvHost &wh, int batch, int n, int m, std::vector<void *> &allocs, WvDev &wd) {
@@ -274,7 +348,7 @@ int wv_upload(const WvHost &wh, int batch, int n, int m, std::vector<void *> &al
 struct WvArgs {
   int n, m, n_e, n_c, nnzA, nnzP, max_iter, check, slice;
   int b0; const int *list;
-  int bs, nb, mid, lpb, n_extra, NS, NV, NSTEP, cst_slots; size_t g_doubles;
+  int bs, nb, mid, lpb, n_extra, NS, NV, NSTEP, cst_slots, NL; size_t g_doubles;      // (NL fills the padding in front of g_doubles)
   double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
   const int *tab;
   double *G, *cst, *wc, *scr; int *ok, *rl_need, *w_ready, *pflag; unsigned long long *it_count;
@@ -326,13 +400,15 @@ __device__ __forceinline__ double wv_wsum(double v) { return wv_wred<false>(v); 
 // ---------------------------------------------------------------------------------------------------------------------
 // factor kernel: value test, twisted block factorisation G_t = Sigma_t^-1, constants of the termination test
 // ---------------------------------------------------------------------------------------------------------------------
+// LNK: link slots per variable slot (0: the kernel of a link-free plan, which holds no code of theirs)
+template <int LNK>
 __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
   const int g = blockIdx.x, lane = threadIdx.x;
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
   if (b < 0) return;
   if (a.setup_active && !a.setup_active[b]) { if (lane == 0) a.rl_need[b] = 0; return; }
   const int n = a.n, m = a.m, bs = a.bs, nb = a.nb, mid = a.mid, NS = a.NS, NV = a.NV, NSTEP = a.NSTEP;
-  const WvTab T = wv_tab_layout(NS, NV);
+  const WvTab T = wv_tab_layout(NS, NV, LNK);
   const int *tab = a.tab;
   const double *ls = a.ls + (size_t)b * m, *us = a.us + (size_t)b * m, *rho = a.rhov + (size_t)b * m;
   const int *w = a.w + (size_t)b * m;
@@ -377,6 +453,14 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
     const int xr = tab[T.xrow * 64 + lane];
     double *c = cst + (size_t)wv_cst_x(NS, NV) * 64 + lane;
     c[0] = xr >= 0 ? 1.0 / E[xr] : 0.0;
+  }
+  if constexpr (LNK > 0) {
+    // link rows sit on the base rho with weight 1 like the box rows (an equality link row has rho_eq: row-local kernel)
+    for (int i = 0; i < NV * LNK; i++) {
+      const int lr = tab[(T.lrow + i) * 64 + lane];
+      if (lr >= 0 && (rho[lr] != rho_base || w[lr] != 1)) bad = 1;
+      cst[(size_t)wv_cst_l(NS, NV, i) * 64 + lane] = lr >= 0 ? 1.0 / E[lr] : 0.0;
+    }
   }
   bad = (int)wv_wmax((double)bad); offd = (int)wv_wmax((double)offd);
   if (lane == 0) a.pflag[b] = offd;
@@ -497,6 +581,30 @@ __device__ __forceinline__ double wv_matvec(double acc, double w, const WvRow<BS
 template <typename T>
 __device__ __forceinline__ const T *wv_opaque(const T *p) { asm volatile("" : "+v"(p)); return p; }
 
+// State and constants of a lane's link slots (qp_admm_wv_kernel, LNK > 0; slot i = v LNK + s): z, y, the clipped delta_y of
+// the checked iteration, x~ of the partners during a row pass; the four constants of a slot (its two A entries, l, u) in
+// registers (REG) or lane-private in LDS at lkl (pairs: piece 2 i = the two A entries, piece 2 i + 1 = l, u; 16 bytes per
+// lane and piece).  The kernel of a link-free plan holds the empty specialisation: nothing of this exists there.
+template <int NV, int LNK, bool REG> struct WvLinks {
+  static constexpr int N = NV * LNK;
+  double alo[REG ? N : 1], ahi[REG ? N : 1], l[REG ? N : 1], u[REG ? N : 1], z[N], y[N], d[N], xp[NV];
+  double *lkl;
+  // The constants of the link slots of variable slot v -- asked for where they are used, one variable slot at a time: fetched
+  // for all slots at the top of a phase they would be 48 live registers on top of the 7-wide instantiations' 460, i.e. scratch.
+  __device__ __forceinline__ void consts(int v, double (&la)[LNK], double (&lh)[LNK], double (&ll)[LNK], double (&lu)[LNK]) const {
+#pragma unroll
+    for (int s = 0; s < LNK; s++) {
+      const int i = v * LNK + s;
+      if constexpr (REG) { la[s] = alo[i]; lh[s] = ahi[i]; ll[s] = l[i]; lu[s] = u[i]; }
+      else {
+        const d2 ca = *(const d2 *)(lkl + (2 * i) * 128), cb = *(const d2 *)(lkl + (2 * i + 1) * 128);
+        la[s] = ca.x; lh[s] = ca.y; ll[s] = cb.x; lu[s] = cb.y;
+      }
+    }
+  }
+};
+template <int NV, bool REG> struct WvLinks<NV, 0, REG> {};
+
 // EXT: the opt-in extensions, in instantiations of their own as in sco_admm_rl.hip: the default kernel (EXT = 0, parity mode)
 // holds no code of theirs.  Bit 0: the solve may start warm (WvArgs::warm); bit 1 (ADAPT): the adaptive-rho variant.
 // ADAPT: the problem's rho is rho_b[b]; at every ad_interval-th iteration, behind the termination test, the kernel forms
@@ -516,9 +624,19 @@ constexpr bool wv_gres_fits(int BS, int NS, int NV, int NSTEP, int LPB, int EXT)
   // against 244, <7,4,3,10,3,3> is at 256 + 256 either way)
   return WV_GRES != 0 && NSTEP % 2 == 0 && !(BS == 7 && (EXT & 2));
 }
-template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
+//
+// LNK: link slots per variable slot (WV_NL; 0 = the kernel of a link-free plan, which holds no code of theirs).  A link row
+// has no slack and two core variables, the same in-block index k of blocks t and t + 1 (a velocity limit).  It belongs to the
+// lane and variable slot of (t, k): z and y in registers, x~ of both ends from the block vectors, the OSQP update of a box row
+// on the base rho.  Its share of the right-hand side for (t, k) joins the slot's own part; the share for (t + 1, k) goes
+// through one more block vector in LDS (oLK, next to the extra rows' oEX), stored in front of the phase's first WV_SYNC and
+// read behind it by the partner.  Every (t + 1, k) has one writer lane, and the rows of a pair add in slot order.
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK>
 __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr bool ADAPT = (EXT & 2) != 0;
+  static_assert(!(LNK > 0 && ADAPT), "adaptive rho on link patterns stays on the row-local kernel (qp_launch_plan)");
+  constexpr int NLK = LNK > 0 ? NV * LNK : 1;           // link slots of a lane
+  constexpr bool LREG = wv_link_regs(BS);
   constexpr bool GRES = wv_gres_fits(BS, NS, NV, NSTEP, LPB, EXT);
   constexpr int HS = (NSTEP + 1) / 2, H2 = NSTEP - HS;
   const int g = blockIdx.x, lane = threadIdx.x;
@@ -540,13 +658,15 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   // pipe (four wavefronts share it), and these rows were a third of a wavefront's LDS bytes per iteration.
   constexpr bool JREG = WV_JREG && NS * BS <= 28;
   constexpr int oG = 0, oEF = oG + NPOS * 64, oEN = oEF + NPOS * 8, oEM = oEN + NPOS * 8, oR = oEM + 8, oXT = oR + NPOS * 8,
-                oXC = oXT + NPOS * 8, oEX = oXC + NPOS * 8, oJ = oEX + NPOS * 8, oPART = oJ + (JREG ? 0 : NS * 512);
+                oXC = oXT + NPOS * 8, oEX = oXC + NPOS * 8, oLK = oEX + NPOS * 8, oJ = oLK + (LNK > 0 ? NPOS * 8 : 0),
+                oPART = oJ + (JREG ? 0 : NS * 512);
+  constexpr int NVEC = LNK > 0 ? 5 : 4;                 // block vectors behind the factor: r, x~, x, extra (, link)
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int *tab0 = a.tab;
   constexpr int oPOS = 0, oHROW = 1, oHBROW = oHROW + NS, oHEVAR = oHBROW + NS, oHEIDX = oHEVAR + NS, oHEPOS = oHEIDX + NS,
                 oHBPOS = oHEPOS + NS, oHJPOS = oHBPOS + NS, oVVAR = oHJPOS + 8 * NS, oVROW = oVVAR + NV, oVPOS = oVROW + NV,
                 oVPK = oVPOS + NV, oVPKM = oVPK + NV, oVPKP = oVPKM + NV, oXROW = oVPKP + NV + 8 * NV + 2 * NV, oXPOS = oXROW + 1,
-                oXPK = oXPOS + 1;
+                oXPK = oXPOS + 1, oLROW = oXPK + 1, oLPLO = oLROW + NV * LNK, oLPHI = oLPLO + NV * LNK;
   const double *As = a.As + (size_t)b * a.nnzA, *qs = a.qs + (size_t)b * n, *lsg = a.ls + (size_t)b * m, *usg = a.us + (size_t)b * m;
   const double *cstg0 = a.cst + (size_t)b * a.cst_slots * 64 + lane;
   double rho_in = a.rho;
@@ -566,15 +686,20 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   {
     const double *Gg = a.G + (size_t)b * a.g_doubles;
     for (int t = lane; t < oR; t += WV_T) lds[t] = Gg[t];
-    for (int t = lane; t < 4 * NPOS * 8; t += WV_T) lds[oR + t] = 0.0;
+    for (int t = lane; t < NVEC * NPOS * 8; t += WV_T) lds[oR + t] = 0.0;
     for (int t = lane; t < NPOS * lpb * 8; t += WV_T) lds[oPART + t] = 0.0;
   }
   // ---- LDS: the constants of the termination test (scalings of the lane's rows and variables, its P entries), lane-minor.
   // They are constants of the solve; as registers (fetched one iteration ahead of every test) they cost 70 VGPRs for the
   // whole launch -- beyond 256 every use of a register is a v_accvgpr move.
+  // (CKG: an instantiation that keeps its link slots' constants in LDS gives them this place -- they are read in every
+  // iteration -- and fetches the constants of the test from global memory at every checked iteration, as the dense P
+  // constants are: with both in LDS the 7-wide plan takes 51 KB, three problems per CU, and a batch of four per CU runs in
+  // two rounds, profiles/wv_link_rows.md)
+  constexpr bool CKG = LNK > 0 && !LREG;
   const int oCK = oPART + NPOS * lpb * 8;
   double *const ckl = lds + oCK + lane;
-  {
+  if constexpr (!CKG) {
 #pragma unroll
     for (int q = 0; q < NS; q++)
 #pragma unroll
@@ -585,9 +710,12 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       for (int k = 0; k < 5; k++) ckl[(3 * NS + 5 * v + k) * 64] = cstg0[(wv_cst_v(NS, v) + k) * 64];
     ckl[(3 * NS + 5 * NV) * 64] = cstg0[wv_cst_x(NS, NV) * 64];
   }
-#define CKH(q, k) ckl[(3 * (q) + (k)) * 64]
-#define CKV(v, k) ckl[(3 * NS + 5 * (v) + (k)) * 64]
-#define CKX ckl[(3 * NS + 5 * NV) * 64]
+#define CKH(q, k) (CKG ? wv_opaque(cstg0)[(wv_cst_h(q) + (k)) * 64] : ckl[(3 * (q) + (k)) * 64])
+#define CKV(v, k) (CKG ? wv_opaque(cstg0)[(wv_cst_v(NS, v) + (k)) * 64] : ckl[(3 * NS + 5 * (v) + (k)) * 64])
+#define CKX (CKG ? wv_opaque(cstg0)[wv_cst_x(NS, NV) * 64] : ckl[(3 * NS + 5 * NV) * 64])
+  // (1/E of a link slot's row comes from global memory at the checked iteration in every instantiation, as the dense P
+  // constants do)
+#define CKL(i) wv_opaque(cstg0)[wv_cst_l(NS, NV, i) * 64]
   // ---- lane roles (row layout): pointers into the vectors of the lane's block
   const int pos_r = tab0[oPOS * 64 + lane];
   double *const xt_p = lds + oXT + pos_r * 2;                                   // x~ of the block, piece 0 (xc: + (oXC - oXT))
@@ -643,6 +771,22 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   const double x_a = x_row >= 0 ? As[tab0[oXPOS * 64 + lane]] : 0.0, x_l = x_row >= 0 ? lsg[x_row] : 0.0, x_u = x_row >= 0 ? usg[x_row] : 0.0;
   const double x_rho = x_row >= 0 ? a.rhov[(size_t)b * m + x_row] : 1.0, x_rinv = 1.0 / x_rho, x_w = x_row >= 0 ? (double)a.w[(size_t)b * m + x_row] : 0.0;
   double x_z = x_row >= 0 && resume ? szg[x_row] : 0.0, x_y = x_row >= 0 && resume ? syg[x_row] : 0.0;
+  // link slots (i = v LNK + s): constants and state; an empty slot is a row of zeros with l = u = 0, its z and y stay 0
+  WvLinks<NV, LNK, LREG> lk;
+  constexpr int NL1 = LNK > 0 ? LNK : 1;
+  if constexpr (LNK > 0) {
+    lk.lkl = lds + oCK + lane * 2;                                    // (!LREG: in the place of the constants of the test, CKG)
+#pragma unroll
+    for (int i = 0; i < NLK; i++) {
+      const int lr = tab0[(oLROW + i) * 64 + lane];
+      d2 ca, cb;
+      ca.x = lr >= 0 ? As[tab0[(oLPLO + i) * 64 + lane]] : 0.0; ca.y = lr >= 0 ? As[tab0[(oLPHI + i) * 64 + lane]] : 0.0;
+      cb.x = lr >= 0 ? lsg[lr] : 0.0; cb.y = lr >= 0 ? usg[lr] : 0.0;
+      if constexpr (LREG) { lk.alo[i] = ca.x; lk.ahi[i] = ca.y; lk.l[i] = cb.x; lk.u[i] = cb.y; }
+      else { *(d2 *)(lk.lkl + (2 * i) * 128) = ca; *(d2 *)(lk.lkl + (2 * i + 1) * 128) = cb; }
+      lk.z[i] = lr >= 0 && resume ? szg[lr] : 0.0; lk.y[i] = lr >= 0 && resume ? syg[lr] : 0.0;
+    }
+  }
   // sweep roles: DPP row 0 (and its copy, row 2) runs chain A, row 1 (and 3) chain B; lane k of a row holds component k
   // (GRES: rows 0 and 1 hold the first HS positions of the two chains, rows 2 and 3 the rest: pos0 is slot 0 of the lane)
   const int srow = lane >> 4, k8 = lane & 7, chain = srow & 1, half = GRES ? srow >> 1 : 0;
@@ -688,6 +832,13 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
 #pragma unroll
       for (int v = 0; v < NV; v++) xtv[v] = v_p[v][0];
       xt[0] = a0.x; xt[1] = a0.y; xt[2] = a1.x; xt[3] = a1.y; xt[4] = a2.x; xt[5] = a2.y; xt[6] = a3.x; xt[7] = a3.y;
+    }
+    // link slots: x~ of the partner (block t + 1, same in-block index)
+    if constexpr (LNK > 0) {
+      if (MODE) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) lk.xp[v] = lds[oXT + v_pkp[v]];
+      }
     }
     double part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     d2 jn0, jn1, jn2, jn3;                       // (rows in LDS) the NEXT slot's row is in flight while this one's arithmetic runs
@@ -796,13 +947,39 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       }
       const double t0 = rho0 * v_z[v] - v_y[v];
       own[v] = v_a[v] * t0 + (sigma * v_x[v] - v_q[v]);
+      if constexpr (LNK > 0) {
+        // the variable's link rows: the update of a box row on a row with two entries; the own end's share joins own[v], the
+        // partner's goes to its place in the link vector (a lane without a partner: zeros into the dummy block)
+        double ps = 0.0, la[NL1], lh[NL1], ll[NL1], lu[NL1];
+        lk.consts(v, la, lh, ll, lu);
+#pragma unroll
+        for (int s = 0; s < LNK; s++) {
+          const int i = v * LNK + s;
+          if (MODE) {
+            const double zt = __builtin_fma(lh[s], lk.xp[v], la[s] * xtv[v]), zr = alpha * zt + oma * lk.z[i];
+            const double zn = wv_min(wv_max(zr + rinv0 * lk.y[i], ll[s]), lu[s]);
+            const double dy = rho0 * (zr - zn);
+            lk.y[i] += dy; lk.z[i] = zn;
+            if (MODE == 2) {
+              const double d1 = upper_is_infinite(lu[s]) ? fmin(dy, 0.0) : dy, dc = lower_is_infinite(ll[s]) ? fmax(d1, 0.0) : d1;
+              c_ndy = fmax(c_ndy, wv_recip(CKL(i)) * fabs(dc)); c_lhs += lu[s] * fmax(dc, 0.0) + ll[s] * fmin(dc, 0.0);
+              lk.d[i] = dc;
+            }
+          }
+          const double t = rho0 * lk.z[i] - lk.y[i];
+          own[v] = __builtin_fma(la[s], t, own[v]); ps = __builtin_fma(lh[s], t, ps);
+        }
+        lds[oLK + v_pkp[v]] = ps;
+      }
     }
     WV_SYNC();
-    // core right-hand side = own part + the extra row's + the block's partial column sums
+    // core right-hand side = own part + the extra row's (+ the link rows' share from block t - 1) + the block's partial
+    // column sums
     double rsum[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) {
       double r = own[v] + v_p[v][oEX - oXT];
+      if constexpr (LNK > 0) r += v_p[v][oLK - oXT];
       const double *pp = v_pp[v];
       if (LPB > 0) {
 #pragma unroll
@@ -995,6 +1172,19 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     }
     WV_SYNC();
     if (x_row >= 0) { x_z = x_a * x_p[oXC - oXT]; x_y = yg[x_row] * cscale / (Eg[x_row] * x_w); }
+    if constexpr (LNK > 0) {
+#pragma unroll
+      for (int v = 0; v < NV; v++) {
+        double la[NL1], lh[NL1], ll[NL1], lu[NL1];
+        lk.consts(v, la, lh, ll, lu);
+#pragma unroll
+        for (int s = 0; s < LNK; s++) {
+          const int i = v * LNK + s, lr = tab0[(oLROW + i) * 64 + lane];
+          lk.z[i] = __builtin_fma(lh[s], lds[oXC + v_pkp[v]], la[s] * v_x[v]);
+          lk.y[i] = lr >= 0 ? yg[lr] * cscale / Eg[lr] : 0.0;
+        }
+      }
+    }
     const double *xq = xt_p + (oXC - oXT);
     const d2 a0 = *(const d2 *)xq, a1 = *(const d2 *)(xq + 2 * NPOS), a2 = *(const d2 *)(xq + 4 * NPOS), a3 = *(const d2 *)(xq + 6 * NPOS);
     const double xc[8] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y, a3.x, a3.y};
@@ -1094,6 +1284,17 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         if (ADAPT && adapt_pt) { v_pri = fmax(v_pri, fabs(ax - x_z)); v_pn = fmax(v_pn, fmax(fabs(x_z), fabs(ax))); }
         if (x_row >= 0) x_p[oEX - oXT] = x_a * (x_w * x_y);
       }
+      // link rows: the partner's share of A'y through the link vector, as in the row phase
+      if constexpr (LNK > 0) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          double ps = 0.0, la[NL1], lh[NL1], ll[NL1], lu[NL1];
+          lk.consts(v, la, lh, ll, lu);
+#pragma unroll
+          for (int s = 0; s < LNK; s++) ps = __builtin_fma(lh[s], lk.y[v * LNK + s], ps);
+          lds[oLK + v_pkp[v]] = ps;
+        }
+      }
       WV_SYNC();
 #pragma unroll
       for (int v = 0; v < NV; v++) {
@@ -1104,6 +1305,19 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         w_pri = fmax(w_pri, e0 * fabs(ax - v_z[v])); w_pn = fmax(w_pn, e0 * fmax(fabs(v_z[v]), fabs(ax)));
         if (ADAPT && adapt_pt) { v_pri = fmax(v_pri, fabs(ax - v_z[v])); v_pn = fmax(v_pn, fmax(fabs(v_z[v]), fabs(ax))); }
         double aty = v_a[v] * v_y[v] + v_p[v][oEX - oXT];
+        if constexpr (LNK > 0) {
+          const double xp = lds[oXC + v_pkp[v]];
+          double la[NL1], lh[NL1], ll[NL1], lu[NL1];
+          lk.consts(v, la, lh, ll, lu);
+          aty += v_p[v][oLK - oXT];
+#pragma unroll
+          for (int s = 0; s < LNK; s++) {
+            const int i = v * LNK + s;
+            const double axl = __builtin_fma(lh[s], xp, la[s] * v_x[v]), el = CKL(i);
+            w_pri = fmax(w_pri, el * fabs(axl - lk.z[i])); w_pn = fmax(w_pn, el * fmax(fabs(lk.z[i]), fabs(axl)));
+            aty = __builtin_fma(la[s], lk.y[i], aty);
+          }
+        }
         const double *pp = v_pp[v];
         if (LPB > 0) {
 #pragma unroll
@@ -1168,10 +1382,27 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
           *(d2 *)part_p = v0; *(d2 *)(part_p + nslot2) = v1; *(d2 *)(part_p + 2 * nslot2) = v2; *(d2 *)(part_p + 3 * nslot2) = v3;
         }
         if (x_row >= 0) x_p[oEX - oXT] = x_a * (x_w * dsv.x);
+        if constexpr (LNK > 0) {
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            double ps = 0.0, la[NL1], lh[NL1], ll[NL1], lu[NL1];
+            lk.consts(v, la, lh, ll, lu);
+#pragma unroll
+            for (int s = 0; s < LNK; s++) ps = __builtin_fma(lh[s], lk.d[v * LNK + s], ps);
+            lds[oLK + v_pkp[v]] = ps;
+          }
+        }
         WV_SYNC();
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           double aty = v_a[v] * dsv.r0[v] + v_p[v][oEX - oXT];
+          if constexpr (LNK > 0) {
+            double la[NL1], lh[NL1], ll[NL1], lu[NL1];
+            lk.consts(v, la, lh, ll, lu);
+            aty += v_p[v][oLK - oXT];
+#pragma unroll
+            for (int s = 0; s < LNK; s++) aty = __builtin_fma(la[s], lk.d[v * LNK + s], aty);
+          }
           const double *pp = v_pp[v];
           if (LPB > 0) {
 #pragma unroll
@@ -1233,6 +1464,16 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
           for (int v = 0; v < NV; v++) {
             const double adx = CKV(v, 1) * (v_a[v] * dsv.var[v]);
             if (v_r0on[v] && ((v_u[v] < WV_BIG && adx > thr) || (v_l[v] > -WV_BIG && adx < -thr))) badv = 1.0;
+            if constexpr (LNK > 0) {
+              const double dxp = lds[oXC + v_pkp[v]];          // delta_x of the partner (an empty slot: 0 inside [0, 0])
+              double la[NL1], lh[NL1], ll[NL1], lu[NL1];
+              lk.consts(v, la, lh, ll, lu);
+#pragma unroll
+              for (int s = 0; s < LNK; s++) {
+                const double adl = CKL(v * LNK + s) * __builtin_fma(lh[s], dxp, la[s] * dsv.var[v]);
+                if (osqp_row_leaves_cone(adl, ll[s], lu[s], thr)) badv = 1.0;
+              }
+            }
           }
           if (x_row >= 0) {
             const double adx = CKX * (x_a * x_p[oXC - oXT]);
@@ -1279,6 +1520,13 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       if (r0 >= 0) { sz[r0] = v_z[v]; sy[r0] = v_y[v]; stp[r0] = rho0 * v_z[v] - v_y[v]; }
     }
     if (x_row >= 0) { sz[x_row] = x_z; sy[x_row] = x_y; stp[x_row] = x_w * (x_rho * x_z - x_y); }
+    if constexpr (LNK > 0) {
+#pragma unroll
+      for (int i = 0; i < NLK; i++) {
+        const int lr = tab[(oLROW + i) * 64 + lane];
+        if (lr >= 0) { sz[lr] = lk.z[i]; sy[lr] = lk.y[i]; stp[lr] = rho0 * lk.z[i] - lk.y[i]; }
+      }
+    }
     if (lane == 0) { a.prog[b] = iter; a.status[b] = 0; a.iters[b] = iter; atomicAdd(a.it_count, (unsigned long long)(iter - it0)); }
     return;
   }
@@ -1305,6 +1553,13 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       if (r0 >= 0) yo[r0] = cinv * Eg[r0] * v_y[v];
     }
     if (x_row >= 0) yo[x_row] = cinv * Eg[x_row] * x_y * x_w;
+    if constexpr (LNK > 0) {
+#pragma unroll
+      for (int i = 0; i < NLK; i++) {
+        const int lr = tab[(oLROW + i) * 64 + lane];
+        if (lr >= 0) yo[lr] = cinv * Eg[lr] * lk.y[i];
+      }
+    }
     if (lane == 0) {
       a.status[b] = status; a.iters[b] = iter; a.resid[2 * (size_t)b] = pri; a.resid[2 * (size_t)b + 1] = dua;
       atomicAdd(a.it_count, (unsigned long long)(iter - it0));
@@ -1320,7 +1575,7 @@ static void wv_fill_args(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, 
   a.n = d.n; a.m = d.m; a.n_e = d.n_e; a.n_c = d.n_c; a.nnzA = d.nnzA; a.nnzP = d.nnzP;
   a.max_iter = aa.max_iter; a.check = aa.check; a.slice = aa.slice; a.b0 = d.b0; a.list = d.list;
   a.bs = wh.bs; a.nb = wh.nb; a.mid = wh.mid; a.lpb = wh.lpb; a.n_extra = wh.n_extra; a.NS = wh.NS; a.NV = wh.NV; a.NSTEP = wh.NSTEP;
-  a.cst_slots = wh.cst_slots; a.g_doubles = wh.g_doubles;
+  a.cst_slots = wh.cst_slots; a.NL = wh.NL; a.g_doubles = wh.g_doubles;
   a.rho = aa.rho; a.sigma = aa.sigma; a.alpha = aa.alpha; a.eps_abs = aa.eps_abs; a.eps_rel = aa.eps_rel;
   a.eps_prim_inf = aa.eps_prim_inf; a.eps_dual_inf = aa.eps_dual_inf;
   a.tab = wd.tab; a.G = wd.G; a.cst = wd.cst; a.wc = wd.wc; a.scr = wd.scr; a.ok = wd.ok; a.rl_need = wd.rl_need; a.w_ready = wd.w_ready; a.pflag = wd.pflag; a.it_count = wd.it_count;
@@ -1362,16 +1617,17 @@ int wv_launch_need(const AdmmArgs &aa, const int *setup_mask, const WvDev &wd, h
 int wv_launch_factor(const AdmmArgs &aa, const int *setup_mask, const WvHost &wh, const WvDev &wd, hipStream_t st) {
   WvArgs a; wv_fill_args(aa, wh, wd, setup_mask, a);
   const int nwg = qp_launch_nwg(aa.d);
-  hipLaunchKernelGGL(qp_wv_factor_kernel, dim3(nwg), dim3(WV_T), 0, st, a);
+  if (wh.NL) hipLaunchKernelGGL(qp_wv_factor_kernel<WV_NL>, dim3(nwg), dim3(WV_T), 0, st, a);
+  else hipLaunchKernelGGL(qp_wv_factor_kernel<0>, dim3(nwg), dim3(WV_T), 0, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
 }
 
-template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT>
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK>
 static int wv_launch_k(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
   static bool attr_done[64] = {};
-  SCO_LDS_ATTR((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>), 64 * 1024, attr_done);
-  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT>), dim3(nwg), dim3(WV_T), lds, st, a);
+  SCO_LDS_ATTR((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK>), 64 * 1024, attr_done);
+  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK>), dim3(nwg), dim3(WV_T), lds, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
 }
@@ -1379,8 +1635,17 @@ static int wv_launch_k(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
 template <int BS, int NS, int NV, int NSTEP, int LPB>
 static int wv_launch_one(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
   // parity mode runs the instantiation without any code of the extensions; the adaptive one can start warm as well
-  if (a.ad_interval > 0) return wv_launch_k<BS, NS, NV, NSTEP, LPB, 3>(a, nwg, lds, st);
-  return a.warm ? wv_launch_k<BS, NS, NV, NSTEP, LPB, 1>(a, nwg, lds, st) : wv_launch_k<BS, NS, NV, NSTEP, LPB, 0>(a, nwg, lds, st);
+  // (a plan with link rows has no adaptive instantiation: qp_launch_plan keeps such launches on the row-local kernel)
+  if (a.NL) {
+    // (nor one with compile-time lanes per block: wv_launch)
+    if (LPB > 0 || a.ad_interval > 0) { sco_set_error("wv_launch: no instantiation with link rows for this launch"); return SCO_ERR_STATE; }
+    // (the 7-wide parity instantiation with link rows, <7,4,3,10,0,0,2>, comes out with 28 B of scratch where the one that
+    // may start warm has none: a cold launch runs on that one, which then takes the same path, a.warm = 0)
+    if constexpr (LPB == 0 && BS == 7) return wv_launch_k<BS, NS, NV, NSTEP, LPB, 1, WV_NL>(a, nwg, lds, st);
+    else if constexpr (LPB == 0) return a.warm ? wv_launch_k<BS, NS, NV, NSTEP, LPB, 1, WV_NL>(a, nwg, lds, st) : wv_launch_k<BS, NS, NV, NSTEP, LPB, 0, WV_NL>(a, nwg, lds, st);
+  }
+  if (a.ad_interval > 0) return wv_launch_k<BS, NS, NV, NSTEP, LPB, 3, 0>(a, nwg, lds, st);
+  return a.warm ? wv_launch_k<BS, NS, NV, NSTEP, LPB, 1, 0>(a, nwg, lds, st) : wv_launch_k<BS, NS, NV, NSTEP, LPB, 0, 0>(a, nwg, lds, st);
 }
 
 int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t st) {
@@ -1388,7 +1653,9 @@ int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t
   const int nwg = qp_launch_nwg(aa.d);
   // the LDS request also fixes how many problems share a CU: at most 4 (one wavefront per SIMD)
   const size_t lds = std::max(wh.lds_bytes, (size_t)36 * 1024);      // (36 KB: never a fifth workgroup on a CU)
-  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3) return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps
+  // (link rows at three lanes per block run on the run-time-lpb instantiation: <7,4,3,10,3> with link rows needs scratch,
+  // profiles/wv_link_rows.md)
+  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3 && !wh.NL) return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps
   if (wh.NSTEP == 10 && wh.NS == 4) return wv_launch_one<7, 4, 3, 10, 0>(a, nwg, lds, st);
   if (wh.NSTEP == 10) return wv_launch_one<8, 2, 2, 10, 0>(a, nwg, lds, st);
   if (wh.NSTEP == 4) return wv_launch_one<8, 1, 1, 4, 0>(a, nwg, lds, st);

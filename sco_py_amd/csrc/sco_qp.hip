@@ -764,8 +764,9 @@ static int qp_choose_tiers(int n, int m, const int *Pp, const int *Pi, const int
     t.kern = QP_K_RL;
     // wavefront tier (one wavefront per problem, block-tridiagonal core solve): patterns of trajectory penalty QPs; it
     // needs the row-local kernel beside it for problems whose values leave the penalty-QP structure, and the Gauss-Jordan
-    // inversion.  The opt-in extensions (warm start, adaptive rho) run on it too
-    t.use_wv = !env.factor_cholesky && !env.no_wv && wv_plan_build(pl, t.wv);
+    // inversion.  The opt-in extensions (warm start, adaptive rho) run on it too; rows that link two neighbouring timesteps
+    // (velocity limits) are allowed, without adaptive rho
+    t.use_wv = !env.factor_cholesky && !env.no_wv && wv_plan_build(pl, t.wv, true);
   } else if (!env.no_reg && reg_caps_for(pl, &CW, &RW, &PX) && reg_plan_build(pl, CW, RW, PX, t.reg)) {
     t.kern = QP_K_REG;
   } else if (!env.no_fast && fast_plan_build(pl, t.fast)) {
@@ -905,13 +906,14 @@ int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
 }
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st) { if (qp->use_wv) (void)hipMemsetAsync(qp->wvd.it_count, 0, sizeof(unsigned long long), st); }
 bool sco_qp_has_wv(const sco_qp *qp) { return qp->use_wv; }
+bool sco_qp_wv_links(const sco_qp *qp) { return qp->use_wv && qp->wv.NL > 0; }
 bool sco_qp_can_adapt(const sco_qp *qp) { return !(qp->use_big && !qp->use_bt); }
 
 // ---- a launch: planned on plain numbers (qp_tier.h), then issued step by step ------------------------------------
 // what the planner needs to know of the handle and the settings
 static QpLaunchIn qp_launch_in(const sco_qp *qp, const sco_qp_settings *st) {
   QpLaunchIn in;
-  in.kern = qp->kern; in.use_big = qp->use_big; in.use_bt = qp->use_bt; in.use_wv = qp->use_wv;
+  in.kern = qp->kern; in.use_big = qp->use_big; in.use_bt = qp->use_bt; in.use_wv = qp->use_wv; in.wv_links = sco_qp_wv_links(qp);
   in.factor_cholesky = qp->factor_cholesky; in.batch = qp->d.batch; in.n_c = qp->d.n_c; in.cus = qp->cus;
   in.adaptive_rho = st->adaptive_rho; in.adaptive_rho_interval = st->adaptive_rho_interval;
   in.adaptive_rho_tolerance = st->adaptive_rho_tolerance; in.check_termination = st->check_termination; in.max_iter = st->max_iter;
@@ -1159,13 +1161,27 @@ extern "C" int sco_debug_rl_plan(int *info) {
   info[0] = ok ? 1 : 0; info[1] = rh.CW; info[2] = rh.TR; info[3] = rh.TC; info[4] = (int)rh.lds_bytes; info[5] = rh.merged ? 1 : 0; info[6] = rh.aligned ? 1 : rh.lay8 ? 2 : 0; info[7] = rh.NS;
   return SCO_OK;
 }
-// Host-only: would that pattern land on the wavefront tier?  info[0] fits, [1] block order, [2] blocks, [3] lanes per block,
-// [4] instantiation BS, [5] NS, [6] NV, [7] NSTEP, [8] LDS bytes, [9] second single rows
-extern "C" int sco_debug_wv_plan(int *info) {
-  WvHost wh;
-  const bool ok = wv_plan_build(g_dbg_plan, wh);
+// Host-only: would that pattern land on the wavefront tier with the link-free plan?  info[0] fits, [1] block order,
+// [2] blocks, [3] lanes per block, [4] instantiation BS, [5] NS, [6] NV, [7] NSTEP, [8] LDS bytes, [9] second single rows
+static bool dbg_wv_plan(bool allow_links, int *info, WvHost &wh) {
+  const bool ok = wv_plan_build(g_dbg_plan, wh, allow_links);
   info[0] = ok ? 1 : 0; info[1] = wh.bs; info[2] = wh.nb; info[3] = wh.lpb; info[4] = wh.BS; info[5] = wh.NS; info[6] = wh.NV;
   info[7] = wh.NSTEP; info[8] = (int)wh.lds_bytes; info[9] = wh.n_extra;
+  return ok;
+}
+extern "C" int sco_debug_wv_plan(int *info) {
+  WvHost wh;
+  dbg_wv_plan(false, info, wh);
+  return SCO_OK;
+}
+// ... and with the plan a handle builds, link rows allowed: the ten fields above, then [10] link rows, [11] link slots per
+// variable slot (0: no link rows), [12] problems per CU, [13] why the plan was refused (WvWhy: 0 accepted, 1 other,
+// 2 link rows not allowed, 3 a third link row on one pair, 4 two core variables of one block without a slack, 5 blocks that
+// are not neighbours, 6 different in-block indices, 7 three or more core variables, 8 LDS, 9 no instantiation for the shape)
+extern "C" int sco_debug_wv_link_plan(int *info) {
+  WvHost wh;
+  dbg_wv_plan(true, info, wh);
+  info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why;
   return SCO_OK;
 }
 // Host-only: the structured global-memory plan of that pattern.  info[0] fits, [1] block order, [2] blocks, [3] block normal

@@ -2055,7 +2055,8 @@ static SqpSchedule sqp_plan(sco_sqp *h, int admm_slice, const sco_qp_settings &q
   in.adaptive_rho = qsl.adaptive_rho; in.max_iter = qsl.max_iter;
   in.adaptive_interval = qsl.adaptive_rho ? sco_qp_adaptive_interval(&qsl) : 0;
   in.supports_groups = sco_qp_supports_groups(h->qp1, &qsl);
-  in.handle_wv = sco_qp_has_wv(h->qp1);
+  // (link rows have no adaptive-rho instantiation on the wavefront tier: the QP layer keeps such launches off it)
+  in.handle_wv = sco_qp_has_wv(h->qp1) && !(qsl.adaptive_rho && sco_qp_wv_links(h->qp1));
   in.wv_min = sco_wv_min_live(in.cus, qsl.adaptive_rho != 0);
   if (in.handle_wv) {                           // (mixed rounds need the wavefront tier; the device is asked once per handle)
     if (!h->xcds) h->xcds = sqp_xcds(h->device, in.cus);
