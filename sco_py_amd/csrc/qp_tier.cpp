@@ -24,6 +24,8 @@ QpCreateEnv qp_create_env() {
 // step on this tier against 285 ms on the row-local kernel (profiles/wv_extensions.md).  The variable still applies when set.
 // A plan with link rows (velocity limits) goes by the same rule as a link-free one: on the 1024-problem 7x20 step every run on
 // this tier was faster than every run on the row-local kernel (profiles/wv_link_rows.md).
+// So does a plan with stacked rows (joint limits: single rows in link slots): 3560 .. 3581 SCO it/s on this tier against
+// 2288 .. 2298 on the row-local kernel, three alternating pairs (profiles/wv_stacked_rows.md).
 int sco_wv_min_live(int cus, bool adaptive) {
   const char *e = getenv("SCO_WV_MIN_PER_CU");
   if (!e && adaptive) return INT_MAX;

@@ -33,7 +33,7 @@ struct QpLaunchIn {
   int kern = QP_K_GENERIC;
   bool use_big = false, use_bt = false;      // global-memory tier / its structured form
   bool use_wv = false;                       // wavefront tier beside the row-local kernel
-  bool wv_links = false;                     // ... and its plan holds link rows (no adaptive-rho instantiation)
+  bool wv_links = false;                     // ... and its plan holds link or stacked rows (no adaptive-rho instantiation)
   bool factor_cholesky = false;
   int batch = 0, n_c = 0;
   int cus = 0;                               // (wv_min comes from it; the planner itself does not read it)

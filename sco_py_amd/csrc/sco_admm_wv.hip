@@ -19,6 +19,11 @@
 // The tier takes patterns with this structure only (wv_plan_build): hinge rows inside one timestep with their slack and its
 // bound row, at most two single rows per core variable, and LINK rows -- no slack, the same in-block index of two
 // neighbouring timesteps, at most WV_NL per pair (velocity limits; the LNK instantiations of the kernel, fixed rho only).
+// More single rows on a variable (joint limits: two one-sided rows next to the trust-box row, and a pin on the first and
+// last timestep) are STACKED rows: the rows in front of the last one sit in the variable's free link slots with an empty
+// partner (lphi = -1, coefficient 0), at most one left-over first row on an extra-row lane.  A stacked row is a link row in
+// everything else: base rho, weight 1, the LNK instantiations, no adaptive rho.  Velocity AND joint limits would need four
+// slots per variable: refused (WV_WHY_STACKED), the row-local kernel runs them.
 // Per problem it takes only VALUES with the structure of a penalty QP (hinge rows l = -inf with one common weight, slack
 // rows [0, inf), everything on the base rho, link rows with weight 1: checked by qp_wv_factor_kernel).  A problem that fails the value test is left to the row-local kernel, which the launcher runs
 // right behind this one for exactly those problems -- so the tier never changes what is solved, only where.
@@ -226,9 +231,42 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
   wh.NL = wh.n_link > 0 ? WV_NL : 0;
   for (int e = 0; e < n_e; e++)
     if (h_of[e] < 0 || b_of[e] < 0 || pl.Ap[pl.elim_var[e] + 1] - pl.Ap[pl.elim_var[e]] != 2) return false;
-  int n_extra = 0;
-  for (int c = 0; c < n_c; c++) { if (single[c].size() > 2) return false; if (single[c].size() == 2) n_extra++; }
-  if (n_extra > WV_T) return false;
+  // ---- single rows.  The variable's own slot takes its LAST single row (the box row: below); xrow[c] is the row it gives to
+  // an extra-row lane, stack[c] the rows it holds in its free link slots
+  int n_extra = 0; bool plain = true;
+  std::vector<int> xrow(n_c, -1);
+  std::vector<std::vector<int>> stack(n_c);
+  for (int c = 0; c < n_c; c++) { if (single[c].size() > 2) plain = false; if (single[c].size() == 2) n_extra++; }
+  if (plain && n_extra <= WV_T) {
+    // at most two single rows per variable and a lane for every second one: the first row of a pair on an extra-row lane
+    for (int c = 0; c < n_c; c++) if (single[c].size() == 2) xrow[c] = single[c][0];
+  } else {
+    // STACKED rows: the rows in front of the last one go into the variable's free link slots, filled from the back, in row
+    // order.  One row may be left over: the variable's first (the place of a pin in the reference's row order), which takes
+    // an extra-row lane.  A variable with two single rows keeps its first one on a lane while lanes last (handed out in
+    // column order, behind the left-over rows), then stacks it.  (A pin that ends up in a slot -- three single rows with both
+    // slots free -- fails the value test, rho_eq: such problems run on the row-local kernel.)
+    if (!allow_links) return false;
+    int n_left = 0;
+    for (int c = 0; c < n_c; c++) {
+      const int k = (int)single[c].size(), free_slots = WV_NL - (int)link[c].size();
+      if (k < 3) continue;
+      if (k - 1 > free_slots + 1) { wh.why = WV_WHY_STACKED; return false; }
+      const int ns = std::min(free_slots, k - 1);
+      stack[c].assign(single[c].end() - 1 - ns, single[c].end() - 1);
+      if (k - 1 > ns) { xrow[c] = single[c][0]; n_left++; }
+    }
+    if (n_left > WV_T) { wh.why = WV_WHY_STACKED; return false; }
+    n_extra = n_left;
+    for (int c = 0; c < n_c; c++) {
+      if (single[c].size() != 2) continue;
+      if (n_extra < WV_T) { xrow[c] = single[c][0]; n_extra++; }
+      else if ((int)link[c].size() < WV_NL) stack[c].push_back(single[c][0]);
+      else { wh.why = WV_WHY_STACKED; return false; }
+    }
+    for (int c = 0; c < n_c; c++) wh.n_stack += (int)stack[c].size();
+  }
+  wh.NL = wh.n_link + wh.n_stack > 0 ? WV_NL : 0;
   // ---- lanes
   int lpb = 0;
   for (int L = 8; L >= 1; L--) if (nb <= 4 * (16 / L)) { lpb = L; break; }
@@ -292,10 +330,17 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
       for (int k2 = 0; k2 < bs; k2++) at(T.vpd + v * 8 + k2, l) = ppos(var, pl.core_var[t * bs + k2]);
       at(T.vpm + v, l) = t > 0 ? ppos(var, pl.core_var[(t - 1) * bs + k]) : -1;
       at(T.vpp + v, l) = t + 1 < nb ? ppos(var, pl.core_var[(t + 1) * bs + k]) : -1;
-      if (single[c].size() == 2) { at(T.xrow, xl) = single[c][0]; at(T.xpos, xl) = apos(single[c][0], var); at(T.xpk, xl) = wv_vidx(npos, p, k); xl++; }
-      for (int s = 0; s < (int)link[c].size(); s++) {               // (link[c] is empty in the last block: c + bs does not exist)
+      if (xrow[c] >= 0) { at(T.xrow, xl) = xrow[c]; at(T.xpos, xl) = apos(xrow[c], var); at(T.xpk, xl) = wv_vidx(npos, p, k); xl++; }
+      const int nlk = (int)link[c].size();
+      for (int s = 0; s < nlk; s++) {                               // (link[c] is empty in the last block: c + bs does not exist)
         const int i = v * wh.NL + s, row = link[c][s];
         at(T.lrow + i, l) = row; at(T.lplo + i, l) = apos(row, var); at(T.lphi + i, l) = apos(row, pl.core_var[c + bs]);
+      }
+      // stacked rows behind them: no partner entry (lphi stays -1, the kernel takes it as coefficient 0), also in the last
+      // block, where the partner's place is the dummy block
+      for (int s = 0; s < (int)stack[c].size(); s++) {
+        const int i = v * wh.NL + nlk + s, row = stack[c][s];
+        at(T.lrow + i, l) = row; at(T.lplo + i, l) = apos(row, var); at(T.lphi + i, l) = -1;
       }
     }
   }
@@ -631,6 +676,9 @@ constexpr bool wv_gres_fits(int BS, int NS, int NV, int NSTEP, int LPB, int EXT)
 // on the base rho.  Its share of the right-hand side for (t, k) joins the slot's own part; the share for (t + 1, k) goes
 // through one more block vector in LDS (oLK, next to the extra rows' oEX), stored in front of the phase's first WV_SYNC and
 // read behind it by the partner.  Every (t + 1, k) has one writer lane, and the rows of a pair add in slot order.
+// A STACKED row (a single row of (t, k) in a link slot: joint limits) is that row without the partner entry: its coefficient
+// there is 0, so what it adds to the link vector, to A'y and to A dx at the partner's place is an exact zero -- also in the
+// last block, whose partner place is the dummy block.
 template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK>
 __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr bool ADAPT = (EXT & 2) != 0;
@@ -778,9 +826,11 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     lk.lkl = lds + oCK + lane * 2;                                    // (!LREG: in the place of the constants of the test, CKG)
 #pragma unroll
     for (int i = 0; i < NLK; i++) {
-      const int lr = tab0[(oLROW + i) * 64 + lane];
+      const int lr = tab0[(oLROW + i) * 64 + lane], lph = tab0[(oLPHI + i) * 64 + lane];
       d2 ca, cb;
-      ca.x = lr >= 0 ? As[tab0[(oLPLO + i) * 64 + lane]] : 0.0; ca.y = lr >= 0 ? As[tab0[(oLPHI + i) * 64 + lane]] : 0.0;
+      // (a stacked row has no partner entry, lphi = -1: coefficient 0.  Every later use of the slot goes through this
+      // constant, so the row's share of the link vector, of A'y and of A dx at the partner's place is an exact zero)
+      ca.x = lr >= 0 ? As[tab0[(oLPLO + i) * 64 + lane]] : 0.0; ca.y = lr >= 0 && lph >= 0 ? As[lph] : 0.0;
       cb.x = lr >= 0 ? lsg[lr] : 0.0; cb.y = lr >= 0 ? usg[lr] : 0.0;
       if constexpr (LREG) { lk.alo[i] = ca.x; lk.ahi[i] = ca.y; lk.l[i] = cb.x; lk.u[i] = cb.y; }
       else { *(d2 *)(lk.lkl + (2 * i) * 128) = ca; *(d2 *)(lk.lkl + (2 * i + 1) * 128) = cb; }

@@ -204,11 +204,15 @@ struct WvHost {
   // slot (0: a link-free plan, the tables and the kernel of such a plan are untouched), problems per CU the LDS leaves room
   // for, and why the plan was refused (WvWhy)
   int n_link = 0, NL = 0, per_cu = SCO_WV_PER_CU, why = 0;
+  // stacked rows (single rows of a core variable other than its last one, held in the variable slot's free link slots with an
+  // empty partner: joint limits).  NL = WV_NL whenever n_link + n_stack > 0
+  int n_stack = 0;
 };
 #define WV_NL 2               // link slots per variable slot: two one-sided rows per joint and transition, or one two-sided row
 // why wv_plan_build refused a pattern (sco_debug_wv_link_plan, info[13])
 enum WvWhy { WV_OK = 0, WV_WHY_OTHER = 1, WV_WHY_LINKS_OFF = 2, WV_WHY_THIRD_LINK = 3, WV_WHY_SAME_BLOCK = 4, WV_WHY_FAR_BLOCKS = 5,
-             WV_WHY_INDEX = 6, WV_WHY_THREE_CORE = 7, WV_WHY_LDS = 8, WV_WHY_SHAPE = 9 };
+             WV_WHY_INDEX = 6, WV_WHY_THREE_CORE = 7, WV_WHY_LDS = 8, WV_WHY_SHAPE = 9,
+             WV_WHY_STACKED = 10 };   // single rows of a variable beyond its free link slots, or beyond the extra-row lanes
 // G: [batch][g_doubles] factor (pivot inverses, couplings); cst: [batch][cst_slots][64] constants of the termination test;
 // wc: [batch] common weight of the hinge rows; ok: [batch] 1 = the problem's values have the penalty-QP structure (else the
 // row-local kernel solves it: rl_need = its setup mask); scr: [batch][m + n] delta_y / delta_x of the last checked iteration
@@ -328,7 +332,7 @@ int sco_qp_launch_sliced(sco_qp *qp, const sco_qp_settings *st, const int *setup
                          int slice, hipEvent_t mid, int *sliced, const QpGroup *grp = nullptr);
 bool sco_qp_supports_groups(const sco_qp *qp, const sco_qp_settings *st);
 bool sco_qp_has_wv(const sco_qp *qp);
-bool sco_qp_wv_links(const sco_qp *qp);   // the handle's wavefront plan holds link rows
+bool sco_qp_wv_links(const sco_qp *qp);   // the handle's wavefront plan holds link or stacked rows (NL > 0)
 int sco_qp_wv_iters(const sco_qp *qp, unsigned long long *out);      // iterations run by the wavefront kernel since the reset
 void sco_qp_wv_iters_reset(sco_qp *qp, hipStream_t st);   // the handle holds the wavefront tier and these settings can use it
 bool sco_qp_can_adapt(const sco_qp *qp);   // false: this handle sits on the dense global-memory tier, which cannot park a solve

@@ -1184,6 +1184,14 @@ extern "C" int sco_debug_wv_link_plan(int *info) {
   info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why;
   return SCO_OK;
 }
+// ... the same fourteen fields (why: also 10 = single rows of a variable beyond its free link slots or beyond the extra-row
+// lanes), then [14] stacked rows: single rows held in a variable slot's link slots with an empty partner
+extern "C" int sco_debug_wv_stack_plan(int *info) {
+  WvHost wh;
+  dbg_wv_plan(true, info, wh);
+  info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why; info[14] = wh.n_stack;
+  return SCO_OK;
+}
 // Host-only: the structured global-memory plan of that pattern.  info[0] fits, [1] block order, [2] blocks, [3] block normal
 // matrices on the matrix cores, [4] why not (BtHost::mf_why), [5] LDS bytes
 extern "C" int sco_debug_bt_plan(int *info) {
