@@ -141,6 +141,32 @@ int sco_qp_adaptive_info(sco_qp *qp, double *rho, int *updates);
  * ms[0] = setup (scaling + factor), ms[1] = ADMM loop. */
 int sco_qp_last_timing(const sco_qp *qp, double ms[2]);
 
+/* ---- polish (opt-in; the reference passes polish=False and keeps a commented-out polish=True next to it,
+ *      osqp_utils.py:208-209) --------------------------------------------------
+ * OSQP's polish step on the result of the handle's last sco_qp_solve, for the problems that ended SCO_QP_SOLVED:
+ * guess the active rows from the ADMM duals (row i is at its lower bound if (A x)_i - l_i < -y_i / w_i, at its upper bound if
+ * u_i - (A x)_i < y_i / w_i: OSQP's tests on one copy of a row of multiplicity w_i, y_i being the multiplier of the whole
+ * row as sco_qp_solve returns it), solve the equality-constrained QP on them through the regularised KKT system
+ * [[P + delta I, Ar'], [Ar, -delta I]] (dense LDL' without pivoting on the device) with refine_iter steps of iterative
+ * refinement against the unregularised system, and keep the polished point only where OSQP's rule accepts it: both
+ * residuals smaller than the solve's, or one smaller while the other one of the solve is under 1e-10.  A row of
+ * multiplicity w enters the system once, with y_i as its unknown.  Float64, no atomics on floating-point data: two runs give the same bits. */
+#define SCO_QP_POLISH_OK       1
+#define SCO_QP_POLISH_FAILED  -1   /* tried, not better: the ADMM solution is kept */
+#define SCO_QP_POLISH_NOT_RUN  0   /* status of the solve was not SCO_QP_SOLVED     */
+typedef struct sco_qp_polish_settings {
+  double delta;        /* OSQP 0.6 default 1e-6                          */
+  int refine_iter;     /* OSQP 0.6 default polish_refine_iter = 3; 0 .. 100 */
+} sco_qp_polish_settings;
+void sco_qp_default_polish_settings(sco_qp_polish_settings *s);
+/* s may be NULL (the defaults).  Outputs (any may be NULL): x[batch][n], y[batch][m], resid[batch][2] as the handle holds
+ * them after the call -- the polished ones where polish_status[batch] is SCO_QP_POLISH_OK (a following warm start begins
+ * there), bit for bit what the solve left elsewhere.  SCO_ERR_STATE without a sco_qp_solve on the values and bounds as they
+ * are loaded now (sco_qp_load and sco_qp_set_bounds discard the result); SCO_ERR_CAPACITY, before anything is launched, for a
+ * pattern with n + m > 1104 (the dense system is built on chip-sized problems: 7-DOF x 20 has n + m = 1094). */
+int sco_qp_polish(sco_qp *qp, const sco_qp_polish_settings *s,
+                  double *x, double *y, int *polish_status, double *resid);
+
 /* ---- SQP layer ---------------------------------------------------------- */
 
 /* Solver knobs, one-to-one with the attributes of sco_py.sco_osqp.solver.Solver

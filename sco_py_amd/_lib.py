@@ -33,6 +33,11 @@ class QpSettings(C.Structure):
     ]
 
 
+class PolishSettings(C.Structure):
+    """struct sco_qp_polish_settings (include/sco_hip.h)."""
+    _fields_ = [("delta", C.c_double), ("refine_iter", C.c_int)]
+
+
 class SqpParams(C.Structure):
     """struct sco_sqp_params (include/sco_hip.h); mirrors Solver attributes."""
     _fields_ = [
@@ -74,6 +79,8 @@ ABI = {
     "sco_qp_info": (C.c_int, [C.c_void_p, _IP]),
     "sco_qp_adaptive_info": (C.c_int, [C.c_void_p, _DP, _IP]),
     "sco_qp_last_timing": (C.c_int, [C.c_void_p, _DP]),
+    "sco_qp_default_polish_settings": (None, [C.POINTER(PolishSettings)]),
+    "sco_qp_polish": (C.c_int, [C.c_void_p, C.POINTER(PolishSettings), _DP, _DP, _IP, _DP]),
     "sco_sqp_default_params": (None, [C.POINTER(SqpParams)]),
     "sco_sqp_create": (C.c_int, [C.c_int, C.POINTER(TrajoptDesc), C.POINTER(C.c_void_p)]),
     "sco_sqp_create_rows": (C.c_int, [C.c_int, C.POINTER(TrajoptDesc), C.c_int, _IP, _IP, _IP, C.POINTER(C.c_void_p)]),
@@ -165,6 +172,16 @@ def default_qp_settings(**kw):
     return s
 
 
+def default_polish_settings(**kw):
+    s = PolishSettings()
+    load().sco_qp_default_polish_settings(C.byref(s))
+    for k, v in kw.items():
+        if not hasattr(s, k):
+            raise TypeError("unknown polish setting %r" % k)
+        setattr(s, k, v)
+    return s
+
+
 def default_sqp_params(**kw):
     p = SqpParams()
     load().sco_sqp_default_params(C.byref(p))
@@ -223,6 +240,26 @@ class BatchedQP(object):
         resid = np.zeros((B, 2))
         check(load().sco_qp_solve(self._h, C.byref(st), dptr(x), dptr(y), iptr(status), iptr(iters), dptr(resid)))
         return x, y[:, : self.m], status, iters, resid
+
+    def polish(self, settings=None):
+        """OSQP's polish step on the result of the last solve (sco_qp_polish): (x, y, polish_status, resid) as the
+        handle holds them afterwards; polish_status 1 = polished, -1 = tried and rejected (the solve's x, y kept),
+        0 = not run (the solve's status was not 1)."""
+        st = settings if settings is not None else default_polish_settings()
+        B = self.batch
+        x = np.zeros((B, self.n)); y = np.zeros((B, max(self.m, 1)))
+        pstat = np.zeros(B, dtype=np.int32); resid = np.zeros((B, 2))
+        check(load().sco_qp_polish(self._h, C.byref(st), dptr(x), dptr(y), iptr(pstat), dptr(resid)))
+        return x, y[:, : self.m], pstat, resid
+
+    def polish_info(self):
+        """HIP-event milliseconds of the last polish by kernel and the active rows per problem (-1: polish did not run)."""
+        lib = load()
+        lib.sco_debug_polish_info.restype = C.c_int
+        lib.sco_debug_polish_info.argtypes = [C.c_void_p, _DP, _IP]
+        ms = np.zeros(4); k = np.zeros(self.batch, dtype=np.int32)
+        check(lib.sco_debug_polish_info(self._h, dptr(ms), iptr(k)))
+        return dict(active_ms=float(ms[0]), assemble_ms=float(ms[1]), factor_ms=float(ms[2]), solve_ms=float(ms[3])), k
 
     def info(self):
         out = np.zeros(4, dtype=np.int32)

@@ -298,7 +298,13 @@ struct sco_qp : QpTiers {
   std::vector<void *> allocs;
   bool loaded = false, solved_once = false;
   double last_ms[2] = {0, 0};
+  // polish (sco_qp_polish.hip): the handle holds the result of a sco_qp_solve on the values and bounds as loaded; the
+  // call's device buffers (allocated by the first one); HIP-event time of the last call by kernel
+  bool polish_ready = false;
+  struct QpPolishBuf *pol = nullptr;
+  double polish_ms[4] = {0, 0, 0, 0};
 };
+void qp_polish_free(sco_qp *qp);        // sco_qp_destroy: the polish buffers are not in `allocs` (the workspace is regrown)
 
 // Internal (device-pointer) entry points used by the SQP layer.
 int sco_qp_create_on_stream(int device, int batch, int n, int m, const int *Pp, const int *Pi,

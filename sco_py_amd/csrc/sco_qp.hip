@@ -852,6 +852,7 @@ extern "C" int sco_qp_destroy(sco_qp *qp) {
   ScoDeviceGuard sco_guard_(qp->device);
   if (qp->stream) (void)hipStreamSynchronize(qp->stream);
   for (void *p : qp->allocs) (void)hipFree(p);
+  qp_polish_free(qp);
   for (auto &e : qp->ev) if (e) (void)hipEventDestroy(e);
   if (qp->own_stream && qp->stream) (void)hipStreamDestroy(qp->stream);
   delete qp;
@@ -880,6 +881,7 @@ extern "C" int sco_qp_load(sco_qp *qp, const double *P_val, const double *q, con
   }
   SCO_HIP(hipStreamSynchronize(qp->stream));
   qp->loaded = true;
+  qp->polish_ready = false;
   return SCO_OK;
 }
 
@@ -887,6 +889,7 @@ extern "C" int sco_qp_set_bounds(sco_qp *qp, const double *l, const double *u) {
   if (!qp || !l || !u) { sco_set_error("sco_qp_set_bounds: null pointer"); return SCO_ERR_ARG; }
   if (!qp->loaded) { sco_set_error("sco_qp_set_bounds: call sco_qp_load first"); return SCO_ERR_STATE; }
   SCO_ON_DEVICE(qp->device);
+  qp->polish_ready = false;
   const QpDev &d = qp->d; const size_t B = d.batch;
   SCO_HIP(hipMemcpyAsync(d.l, l, B * d.m * sizeof(double), hipMemcpyHostToDevice, qp->stream));
   SCO_HIP(hipMemcpyAsync(d.u, u, B * d.m * sizeof(double), hipMemcpyHostToDevice, qp->stream));
@@ -1064,6 +1067,7 @@ extern "C" int sco_qp_solve(sco_qp *qp, const sco_qp_settings *settings, double 
     sco_set_error("sco_qp_solve: bad settings"); return SCO_ERR_ARG;
   }
   SCO_ON_DEVICE(qp->device);
+  qp->polish_ready = false;            // until this solve has ended
   const QpDev &d = qp->d; const size_t B = d.batch;
   int rc;
   if (settings->adaptive_rho) {
@@ -1090,6 +1094,7 @@ extern "C" int sco_qp_solve(sco_qp *qp, const sco_qp_settings *settings, double 
     }
     SCO_TRY(qp_copy_back(qp, x, y, status, iters, resid));
     qp->last_ms[0] = ms_setup; qp->last_ms[1] = ms_admm;
+    qp->polish_ready = true;
     return SCO_OK;
   }
   rc = sco_qp_launch(qp, settings, nullptr, nullptr);
@@ -1099,6 +1104,7 @@ extern "C" int sco_qp_solve(sco_qp *qp, const sco_qp_settings *settings, double 
   SCO_HIP(hipEventElapsedTime(&ms0, qp->ev[0], qp->ev[1]));
   SCO_HIP(hipEventElapsedTime(&ms1, qp->ev[1], qp->ev[2]));
   qp->last_ms[0] = ms0; qp->last_ms[1] = ms1;
+  qp->polish_ready = true;
   return SCO_OK;
 }
 

@@ -98,7 +98,7 @@ def solve_many(probs, solver_factory=None, method="penalty_sqp", **solve_kwargs)
     if solve_kwargs.get("tol") is not None:                 # Q8, as Solver.solve does it
         lead.min_trust_region_size = lead.min_approx_improve = lead.cnt_tolerance = solve_kwargs["tol"]
     host = list(range(len(probs)))
-    if lead.device_loop and lead._runs_reference_control_flow():
+    if lead.device_loop and not solve_kwargs.get("polish") and lead._runs_reference_control_flow():   # (no polish in sco_sqp_*)
         t0 = time.perf_counter()
         buckets, host = {}, []
         for k, p in enumerate(probs):

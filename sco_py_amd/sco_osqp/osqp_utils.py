@@ -246,12 +246,15 @@ def _cached_handle(B, n, m, P0, A0):
 def _solve_qp_batch(requests):
     """Solve a list of QPs that share ONE sparsity pattern and one settings tuple in a
     single device launch.  Each request is a dict with P, q, A, l, u, w (row weights or
-    None) and settings = (eps_abs, eps_rel, max_iter, rho, sigma, adaptive_rho).
-    Returns a list of (x, status, iters)."""
+    None) and settings = (eps_abs, eps_rel, max_iter, rho, sigma, adaptive_rho), with a seventh entry 1.0 when the
+    requests ask for polish (a request without it keeps the six-entry tuple its consumers take apart).
+    Returns a list of (x, status, iters); with polish, of (x, status, iters, polish_status) where x is the handle's x
+    after sco_qp_polish."""
     r0 = requests[0]
     P0, A0 = r0["P"], r0["A"]
     n, m = A0.shape[1], A0.shape[0]
-    eps_abs, eps_rel, max_iter, rho, sigma, adaptive_rho = r0["settings"]
+    eps_abs, eps_rel, max_iter, rho, sigma, adaptive_rho = r0["settings"][:6]
+    polish = len(r0["settings"]) > 6 and bool(r0["settings"][6])
     B = len(requests)
     Pv = np.stack([r["P"].data for r in requests]) if P0.nnz else np.zeros((B, 0))
     Av = np.stack([r["A"].data for r in requests]) if A0.nnz else np.zeros((B, 0))
@@ -266,18 +269,26 @@ def _solve_qp_batch(requests):
             qp.load(Pv, np.stack([r["q"] for r in requests]), Av,
                     np.stack([r["l"] for r in requests]), np.stack([r["u"] for r in requests]), w)
             x, _y, status, iters, _res = qp.solve(st)
+            if polish:
+                x, _y, pstat, _res = qp.polish()
         except Exception:
             _HANDLE_CACHE.popitem()              # do not keep a handle that failed
             qp.close()
             raise
+    if polish:
+        return [(x[b], int(status[b]), int(iters[b]), int(pstat[b])) for b in range(B)]
     return [(x[b], int(status[b]), int(iters[b])) for b in range(B)]
 
 
-def _solve_qp(P, q, A, l, u, eps_abs, eps_rel, max_iter, rho, sigma, w=None, adaptive_rho=False):
+def _solve_qp(P, q, A, l, u, eps_abs, eps_rel, max_iter, rho, sigma, w=None, adaptive_rho=False, polish=False):
     """One QP on the GPU through the C ABI.  Inside ``batching.solve_many`` the call is
     parked until every concurrently running solve has reached its next QP, and QPs with
-    the same pattern go to the device together.  Returns (x, status, iters)."""
-    req = dict(P=P, q=q, A=A, l=l, u=u, w=w, settings=(eps_abs, eps_rel, max_iter, rho, sigma, 1.0 if adaptive_rho else 0.0))
+    the same pattern go to the device together.  Returns (x, status, iters), with ``polish``
+    (x, status, iters, polish_status)."""
+    settings = (eps_abs, eps_rel, max_iter, rho, sigma, 1.0 if adaptive_rho else 0.0)
+    if polish:
+        settings += (1.0,)        # polished and unpolished requests never share a launch
+    req = dict(P=P, q=q, A=A, l=l, u=u, w=w, settings=settings)
     from . import batching
     server = batching.current_server()
     if server is not None:
@@ -299,19 +310,29 @@ def optimize(
     adaptive_rho: bool = DEFAULT_ADAPTIVE_RHO,
     sigma: float = DEFAULT_SIGMA,
     verbose: bool = False,
+    polish: bool = False,
 ):
     """Assemble the current QP and solve it (osqp_utils.py:113-221).
 
     Returns ``(solve_res, var_to_index_dict)``; callers read ``solve_res.x`` and
-    ``solve_res.info.status_val`` (prob.py:197, 202)."""
+    ``solve_res.info.status_val`` (prob.py:197, 202).
+
+    ``polish`` (the reference passes ``polish=False`` to OSQP, osqp_utils.py:208-209): run OSQP's polish step on a
+    solved QP (``sco_qp_polish``); ``solve_res.x`` is then the polished point where ``solve_res.info.status_polish``
+    is 1, the ADMM answer where it is -1 (polish rejected) or 0 (not asked for, or the QP was not solved)."""
     uniq_cnts, counts = fold_repeated_constraints(osqp_lin_cnt_exprs)
     P, q, A, l, u, index = assemble_qp(osqp_vars, osqp_quad_objs, osqp_lin_objs, uniq_cnts)
     w = None
     if counts.size and int(counts.max()) > 1:
         w = np.concatenate([counts, np.ones(len(osqp_vars), dtype=np.int32)])     # bound rows appear once
-    x, status, iters = _solve_qp(P, q, A, l, u, eps_abs, eps_rel, max_iter, rho, sigma, w=w,
-                                 adaptive_rho=bool(adaptive_rho))
-    solve_res = SimpleNamespace(x=x, info=SimpleNamespace(status_val=status, iter=iters))
+    if polish:
+        x, status, iters, status_polish = _solve_qp(P, q, A, l, u, eps_abs, eps_rel, max_iter, rho, sigma, w=w,
+                                                    adaptive_rho=bool(adaptive_rho), polish=True)
+    else:
+        x, status, iters = _solve_qp(P, q, A, l, u, eps_abs, eps_rel, max_iter, rho, sigma, w=w,
+                                     adaptive_rho=bool(adaptive_rho))
+        status_polish = 0
+    solve_res = SimpleNamespace(x=x, info=SimpleNamespace(status_val=status, iter=iters, status_polish=status_polish))
     if status == -2 and verbose:
         print("ERROR! OSQP Solver hit max iteration limit. Either reduce your tolerances "
               "or increase the max iterations!")

@@ -123,9 +123,12 @@ class Prob(object):
                  rho: float = osqp_utils.DEFAULT_RHO,
                  adaptive_rho: bool = osqp_utils.DEFAULT_ADAPTIVE_RHO,
                  sigma: float = osqp_utils.DEFAULT_SIGMA,
-                 verbose=False):
+                 verbose=False,
+                 polish=False):
         """Solve the current QP; on success scatter the solution into the
-        variables and fire the callback (prob.py:146-205)."""
+        variables and fire the callback (prob.py:146-205).  ``polish``: OSQP's polish step on
+        the solved QP (``osqp_utils.optimize``; the reference keeps it switched off)."""
+        extra = dict(polish=True) if polish else {}
         lin_objs = self._osqp_lin_objs
         cnts = self._osqp_lin_cnt_exprs
         if add_convexified_terms:
@@ -136,7 +139,7 @@ class Prob(object):
         solve_res, var_to_index_dict = osqp_utils.optimize(
             self._osqp_vars, self._vars, self._osqp_quad_objs, lin_objs, cnts,
             osqp_eps_abs, osqp_eps_rel, osqp_max_iter,
-            rho=rho, adaptive_rho=adaptive_rho, sigma=sigma, verbose=verbose,
+            rho=rho, adaptive_rho=adaptive_rho, sigma=sigma, verbose=verbose, **extra
         )
         if solve_res.info.status_val not in [1, 2]:      # prob.py:197
             return False

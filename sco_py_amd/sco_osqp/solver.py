@@ -123,16 +123,23 @@ class Solver(object):
               rho: float = osqp_utils.DEFAULT_RHO,
               adaptive_rho: bool = osqp_utils.DEFAULT_ADAPTIVE_RHO,
               sigma: float = osqp_utils.DEFAULT_SIGMA,
+              polish: bool = False,
               ):
         """Whether the solve succeeded (solver.py:30-59).  ``tol`` permanently overwrites three thresholds of
-        this instance (Q8), also when the method is then rejected."""
+        this instance (Q8), also when the method is then rejected.
+
+        ``polish=True`` runs OSQP's polish step on every penalty QP (``Prob.optimize``; the projection QP keeps the
+        default settings, Q7).  Such a solve always takes the host loop: the compiled device-resident loop
+        (``sco_sqp_*``) has no polish."""
         if tol is not None:
             self.min_trust_region_size = self.min_approx_improve = self.cnt_tolerance = tol
         if method != "penalty_sqp":
             raise Exception("This method is not supported.")
         qp_kw = dict(osqp_eps_abs=osqp_eps_abs, osqp_eps_rel=osqp_eps_rel, osqp_max_iter=osqp_max_iter, rho=rho,
                      adaptive_rho=adaptive_rho, sigma=sigma)
-        if self.device_loop and self._runs_reference_control_flow():
+        if polish:
+            qp_kw["polish"] = True
+        if self.device_loop and not polish and self._runs_reference_control_flow():
             # a Prob whose non-linear expressions are device expressions runs the WHOLE solve in the device-resident
             # loop (sco_sqp_*); anything else keeps the host loop below with one device QP per optimize
             from . import compile as sco_compile
@@ -140,8 +147,7 @@ class Solver(object):
             if cp is not None:
                 return self._solve_compiled([prob], [cp], verbose=verbose, **qp_kw)[0]
         self.last_path = "host"
-        return self._penalty_sqp(prob, verbose=verbose, osqp_eps_abs=osqp_eps_abs, osqp_eps_rel=osqp_eps_rel,
-                                 osqp_max_iter=osqp_max_iter, rho=rho, adaptive_rho=adaptive_rho, sigma=sigma)
+        return self._penalty_sqp(prob, verbose=verbose, **qp_kw)
 
     # ------------------------------------------------------------------ device-resident loop
     def _runs_reference_control_flow(self):
