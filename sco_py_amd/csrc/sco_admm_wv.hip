@@ -66,6 +66,9 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #ifndef WV_GRES
 #define WV_GRES 1             // 0 = every instantiation on the LDS-fed sweep (scripts/build_ablate.py wv:WV_GRES=0)
 #endif
+#ifndef WV_ROWS_EARLY
+#define WV_ROWS_EARLY 1       // 0 = the row phase reads its partial sums behind the core-variable loop, as before (scripts/build_ablate.py wv:WV_ROWS_EARLY=0)
+#endif
 #if WV_VARIANT == 1
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
 #endif
@@ -669,6 +672,15 @@ constexpr bool wv_gres_fits(int BS, int NS, int NV, int NSTEP, int LPB, int EXT)
   // against 244, <7,4,3,10,3,3> is at 256 + 256 either way)
   return WV_GRES != 0 && NSTEP % 2 == 0 && !(BS == 7 && (EXT & 2));
 }
+// The row phase with its partial-sum reads in ONE batch behind the first WV_SYNC, in front of the core-variable loop, which
+// needs none of them: the round trip runs under that loop's arithmetic instead of in front of the sums.  The
+// batch is NV x (LPB + 1) live doubles across the loop: an instantiation takes this order where it fits without scratch and
+// without more accumulation registers than before (profiles/wv_row_handover.md).  Link plans store oLK inside the variable
+// loop and run-time lanes per block loop over lpb: both keep the old order.
+constexpr bool wv_rows_early(int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK) {
+  // (<7,4,3,10,3,3> is at 256 + 256 registers as it is: the adaptive-rho instantiations keep the old order)
+  return WV_ROWS_EARLY != 0 && LNK == 0 && LPB > 0 && !(EXT & 2);
+}
 //
 // LNK: link slots per variable slot (WV_NL; 0 = the kernel of a link-free plan, which holds no code of theirs).  A link row
 // has no slack and two core variables, the same in-block index k of blocks t and t + 1 (a velocity limit).  It belongs to the
@@ -686,6 +698,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr int NLK = LNK > 0 ? NV * LNK : 1;           // link slots of a lane
   constexpr bool LREG = wv_link_regs(BS);
   constexpr bool GRES = wv_gres_fits(BS, NS, NV, NSTEP, LPB, EXT);
+  constexpr bool EARLY = wv_rows_early(BS, NS, NV, NSTEP, LPB, EXT, LNK);
   constexpr int HS = (NSTEP + 1) / 2, H2 = NSTEP - HS;
   const int g = blockIdx.x, lane = threadIdx.x;
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
@@ -974,6 +987,19 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       const double t = x_w * (x_rho * x_z - x_y);
       if (x_row >= 0) x_p[oEX - oXT] = x_a * t;
     }
+    // EARLY: every read of the sums is issued here, back to back, and the scheduler may move nothing of the variable loop in
+    // front of them, nor them behind it: the loop's ~60 instructions run while the reads are on their way
+    double s_ex[NV], s_pt[NV][LPB > 0 ? LPB : 1];
+    if constexpr (EARLY) {
+      WV_SYNC();
+#pragma unroll
+      for (int v = 0; v < NV; v++) {
+        s_ex[v] = v_p[v][oEX - oXT];
+#pragma unroll
+        for (int s2 = 0; s2 < LPB; s2++) s_pt[v][s2] = v_pp[v][s2 * 2];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     // core variables: box row, x update, own part of the right-hand side
     double own[NV];
 #pragma unroll
@@ -1022,16 +1048,19 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         lds[oLK + v_pkp[v]] = ps;
       }
     }
-    WV_SYNC();
+    if constexpr (EARLY) __builtin_amdgcn_sched_barrier(0); else WV_SYNC();
     // core right-hand side = own part + the extra row's (+ the link rows' share from block t - 1) + the block's partial
     // column sums
     double rsum[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) {
-      double r = own[v] + v_p[v][oEX - oXT];
+      double r = own[v] + (EARLY ? s_ex[v] : v_p[v][oEX - oXT]);
       if constexpr (LNK > 0) r += v_p[v][oLK - oXT];
       const double *pp = v_pp[v];
-      if (LPB > 0) {
+      if (EARLY) {
+#pragma unroll
+        for (int s2 = 0; s2 < LPB; s2++) r += s_pt[v][s2];
+      } else if (LPB > 0) {
 #pragma unroll
         for (int s2 = 0; s2 < LPB; s2++) r += pp[s2 * 2];
       } else {
