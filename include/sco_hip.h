@@ -482,6 +482,22 @@ int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]);
 int sco_debug_sqp_schedule(const int in[12], int plan[20], const int round_in[3], int round_out[8]);
 int sco_debug_stage_sweep(int n, const double *begin_ms, const double *end_ms, const int *stage, double ms[5]);
 
+/* The problem layout of the SQP layer on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/sqp_layout.h).
+ * sco_debug_sqp_layout: the descriptor and (n_rows > 0) the general rows' pattern as for sco_sqp_create_rows; refused with
+ * the same code and sco_last_error text.  dims[22] = {NE, span, span * dof, blocks, n_eq_rows, pin rows, velocity rows,
+ * joint-limit rows, general rows, their entries, rows per block, n_x, slacks, n, linear rows, non-linear rows, m, blocks with
+ * the reach block, history stride, row family (0 arm, 1 point, 2 quadratic, 3 program), objective kind (0 none, 1 end
+ * effector, 2 program per timestep, 3 program per block), acceleration term}; sizes[15] = the lengths of, in this order,
+ * Pp, Pi, Ap, Ai of the projection QP, Pp, Pi, Ap, Ai of the penalty QP, jpos, epos, ppos, gpos0, gpos1 (position tables
+ * into the penalty QP's values; gpos0 into the projection QP's A values) and of the constant A values of the projection
+ * and the penalty QP.  ints / vals: NULL, or room for the thirteen int vectors / the two double vectors back to back.
+ * sco_debug_sqp_check_program: the checks of sco_sqp_load_program{,_steps} on a program for a handle of this descriptor
+ * after sco_sqp_set_circle_rows(n_circle_rows); returns their code. */
+int sco_debug_sqp_layout(const sco_trajopt_desc *desc, int n_rows, const int *row_ptr, const int *col_idx, const int *row_is_eq,
+                         int dims[22], int sizes[15], int *ints, double *vals);
+int sco_debug_sqp_check_program(const sco_trajopt_desc *desc, int n_circle_rows, int n_words, const int *words, const int *row_ptr,
+                                int n_consts, int n_params);
+
 /* What a launch on a QP handle does, on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/qp_tier.h).
  * sco_debug_qp_launch_plan: in[24] = {on-chip kernel of the handle (0 row-local, 1 register-offset, 2 sliced-ELL, 3 generic),
  * global-memory tier, its structured form, wavefront tier (2: its plan holds link rows), Cholesky cross-check (0 / 1 each),

@@ -12,8 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libsco_hip.so")
 SOURCES = ["sco_qp.hip", "sco_admm_fast.hip", "sco_admm_reg.hip", "sco_admm_rl.hip", "sco_admm_wv.hip", "sco_qp_big.hip", "sco_sqp.hip", "sco_qp_polish.hip",
-           "qp_plan.cpp", "qp_tier.cpp", "sqp_sched.cpp", "qp_polish_plan.cpp"]
-HEADERS = ["sco_internal.h", "sco_admm_check.h", "qp_plan.h", "qp_tier.h", "sqp_sched.h", "qp_polish_plan.h", os.path.join("..", "..", "include", "sco_hip.h")]
+           "qp_plan.cpp", "qp_tier.cpp", "sqp_sched.cpp", "sqp_layout.cpp", "qp_polish_plan.cpp"]
+HEADERS = ["sco_internal.h", "sco_admm_check.h", "qp_plan.h", "qp_tier.h", "sqp_sched.h", "sqp_layout.h", "sqp_rows.h", "qp_polish_plan.h", os.path.join("..", "..", "include", "sco_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

@@ -109,6 +109,8 @@ ABI = {
     "sco_debug_wv_gres_slot": (C.c_int, [C.c_int, C.c_int, _IP]),
     "sco_debug_sqp_schedule": (C.c_int, [_IP, _IP, _IP, _IP]),
     "sco_debug_stage_sweep": (C.c_int, [C.c_int, _DP, _DP, _IP, _DP]),
+    "sco_debug_sqp_layout": (C.c_int, [C.POINTER(TrajoptDesc), C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _DP]),
+    "sco_debug_sqp_check_program": (C.c_int, [C.POINTER(TrajoptDesc), C.c_int, C.c_int, _IP, _IP, C.c_int, C.c_int]),
     "sco_debug_qp_launch_plan": (C.c_int, [_IP, _DP, _IP]),
     "sco_debug_plan_tiers": (C.c_int, [_IP]),
     "sco_sqp_solve": (C.c_int, [C.c_void_p, C.POINTER(SqpParams), C.POINTER(QpSettings)]),

@@ -25,7 +25,13 @@
 // One workgroup of 256 threads per problem; problems are independent, so there is
 // no inter-workgroup communication.  The host only reads one "active problems"
 // counter per round.
+//
+// This file holds the round kernels, the handle, the loaders and the round loop.  What a row or an objective term of a
+// family IS (value, gradient, violation) lives in sqp_rows.h; which descriptors and programs are accepted, every
+// dimension, the QP patterns and the position tables are host arithmetic in sqp_layout.{h,cpp}.
 #include "sco_admm_check.h"
+#include "sqp_layout.h"
+#include "sqp_rows.h"
 #include "sqp_sched.h"
 
 #include <algorithm>
@@ -36,8 +42,6 @@
 #include <cstring>
 
 #define NWAVE (SCO_BLOCK / 64)
-#define FD_LEVELS 4
-#define FD_BASE (1.0 / 64.0)
 
 enum { ST_PROJECT = 0, ST_CONVEXIFY = 1, ST_TRIAL = 2, ST_DONE = 3 };
 enum { STEP_PROJECT = 0, STEP_ACCEPT = 1, STEP_SHRINK = 2, STEP_YCONV = 3, STEP_XCONV = 4, STEP_BAD = 5, STEP_GROUP = 6 };
@@ -76,10 +80,9 @@ struct SqpDev {
   // ds = S d numbers x[t d .. t d + ds) (consecutive timesteps are contiguous), there are NBt = T - S + 1 of them, and the
   // last Req of a block's R rows are equalities (r03).  Arm / point families: S = 1, ds = d, NBt = T, Req = 0.
   int S, ds, NBt, Req;
-  int point;         // 1 SCO_FAM_POINT_CIRCLES: the rows are distances of the point x[0:2] itself (no arm kinematics);
-                     // 2 SCO_FAM_STATE_QUADRATIC: general quadratic rows with the coefficients below
-  double *qQ, *qa, *qc;   // [B][O][d*d], [B][O][d], [B][O]
-                     // 3 SCO_FAM_STATE_PROGRAM: rows as postfix programs (shared) over the state and per-problem parameters
+  int point;         // RowFamily (sqp_layout.h): which model the non-linear rows follow
+  double *qQ, *qa, *qc;   // ROWS_QUADRATIC: [B][O][d*d], [B][O][d], [B][O]
+                     // ROWS_PROGRAM: words, row starts and constants (shared), parameters per problem
   const int *pw, *pptr; const double *pconst; const double *ppar; int n_par;
   int R1;            // r04 (SCO_FAM_STATE_PROGRAM): the first R1 rows of a block are keep-out rows of the point (x[0], x[1]) against
                      // obstacles[b][0 .. R1) as in SCO_FAM_POINT_CIRCLES -- a SECOND kind of non-linear rows on the same Variable
@@ -101,10 +104,9 @@ struct SqpDev {
   // SCO_FAM_FLAG_EE_COST: non-quadratic objective term weight * ||ee(theta_t) - target||^2 per timestep, convexified to
   // degree 2 every SQP iteration (expr.py:143-153): oH = Hessian after the eigenvalue shift, oA, ob = the model's
   // linear and constant part; ppos = position in qp1's P values of entry (row (t, 0), column (t, j))
-  int cost;          // 1 = the arm's end-effector term, 2 = an objective PROGRAM (SCO_FAM_FLAG_OBJ_PROGRAM: program index R),
-                     // 3 = an objective program per constraint BLOCK (SCO_FAM_FLAG_OBJ_BLOCK: program index R, state ds, NBt terms)
+  int cost;          // ObjKind (sqp_layout.h)
   double *cw, *ctgt, *oH, *oA, *ob;   // [B], [B][2], [B][NO][dO*dO], [B][NO][dO], [B][NO] (NO, dO = T, d or NBt, ds)
-  const int *ppos;                    // [n_x]; cost 3: entry (r, c) of the dense band sits at ppos[c] + r
+  const int *ppos;                    // [n_x]; OBJ_BLOCK: entry (r, c) of the dense band sits at ppos[c] + r
   const double *a0c, *a1c;      // constant parts of the A values of the projection / penalty QP (shared)
   double *vmax;                 // [B]
   double *jlo, *jhi;            // [B][d]
@@ -129,7 +131,6 @@ struct SqpDev {
   double *mvec;                   // [B][32] per-group violation at the convexification point
   unsigned int *nonconv;          // [B] prob.nonconverged_groups: the violated groups under the y threshold (solver.py:232-234)
   unsigned int *stalled;          // [B] the groups that ended the minimisation (solver.py:209-228); the reference lists them first
-  const int *bpos;   // CSC positions are not needed for bounds: rows are contiguous
   // Q3 emulation: per timestep block, the points already seen (keys = rint(x * 1e6), the
   // reference's tuple(x.round(6))) with their f values, and the points already
   // convexified with their affine model
@@ -157,7 +158,6 @@ struct sco_sqp {
   void *prog_buf[4] = {nullptr, nullptr, nullptr, nullptr};   // sco_sqp_load_program: words, row starts, constants, parameters
   void *objw_buf = nullptr;                                    // sco_sqp_load_obj_weights
   void *accw_buf = nullptr;                                    // sco_sqp_load_acc_weights
-  std::vector<int> gen_ptr, gen_col, gen_iseq;                 // sco_sqp_create_rows: the general affine rows' pattern
   bool gen_loaded = false;
   size_t prog_bytes[4] = {0, 0, 0, 0};
   bool loaded = false, solved = false, target_loaded = false, vel_loaded = false, jl_loaded = false, cost_loaded = false, quad_loaded = false, prog_loaded = false;
@@ -198,264 +198,6 @@ __device__ __forceinline__ void block_reduce_sm(double (&v)[NS + NM], double *re
   }
 }
 
-// SCO_FAM_ARM_CIRCLES: row (k, o) of one timestep block,
-//   g = r_o - || p_k(theta) - c_o ||,  p_k = planar forward kinematics.
-// `pert` >= 0 adds `h` to joint `pert` (finite differences).
-__device__ __forceinline__ double arm_row(const double *th, const double *len, int lk, double frac,
-                                          double cx, double cy, double rad, int pert, double h) {
-  double phi = 0.0, px = 0.0, py = 0.0;
-  for (int i = 0; i <= lk; i++) {
-    double a = th[i];
-    if (i == pert) a += h;
-    phi += a;
-    double s, c;
-    sincos(phi, &s, &c);
-    const double L = (i == lk) ? frac * len[i] : len[i];
-    px += L * c; py += L * s;
-  }
-  const double dx = px - cx, dy = py - cy;
-  return rad - sqrt(dx * dx + dy * dy);
-}
-
-// analytic d g / d theta_j of the same row
-__device__ __forceinline__ double arm_row_grad(const double *th, const double *len, int lk, double frac,
-                                               double cx, double cy, int j) {
-  if (j > lk) return 0.0;
-  double phi = 0.0, px = 0.0, py = 0.0, sx = 0.0, sy = 0.0;
-  for (int i = 0; i <= lk; i++) {
-    phi += th[i];
-    double s, c;
-    sincos(phi, &s, &c);
-    const double L = (i == lk) ? frac * len[i] : len[i];
-    px += L * c; py += L * s;
-    if (i >= j) { sx += -L * s; sy += L * c; }
-  }
-  const double dx = px - cx, dy = py - cy;
-  return -(dx * sx + dy * sy) / sqrt(dx * dx + dy * dy);
-}
-
-// SCO_FAM_ARM_REACH: component `comp` (0 = x, 1 = y) of the end-effector position
-__device__ __forceinline__ double arm_ee(const double *th, const double *len, int d, int comp, int pert, double h) {
-  double phi = 0.0, p = 0.0;
-  for (int i = 0; i < d; i++) {
-    double a = th[i];
-    if (i == pert) a += h;
-    phi += a;
-    double sn, cs;
-    sincos(phi, &sn, &cs);
-    p += len[i] * (comp == 0 ? cs : sn);
-  }
-  return p;
-}
-__device__ __forceinline__ double arm_ee_grad(const double *th, const double *len, int d, int comp, int j) {
-  double phi = 0.0, g = 0.0;
-  for (int i = 0; i < d; i++) {
-    phi += th[i];
-    double sn, cs;
-    sincos(phi, &sn, &cs);
-    if (i >= j) g += comp == 0 ? -(len[i] * sn) : len[i] * cs;
-  }
-  return g;
-}
-
-// SCO_FAM_FLAG_EE_COST: weight * ||ee(theta) - target||^2 with up to two perturbed coordinates (finite differences)
-__device__ __forceinline__ double arm_ee_cost(const double *th, const double *len, int d, double tx, double ty, double w,
-                                              int pi, double hi, int pj, double hj) {
-  double phi = 0.0, ex = 0.0, ey = 0.0;
-  for (int i = 0; i < d; i++) {
-    double a = th[i];
-    if (i == pi) a += hi;
-    if (i == pj) a += hj;
-    phi += a;
-    double sn, cs;
-    sincos(phi, &sn, &cs);
-    ex += len[i] * cs; ey += len[i] * sn;
-  }
-  ex -= tx; ey -= ty;
-  return w * (ex * ex + ey * ey);
-}
-
-// Richardson extrapolation of a central-difference ladder (halving steps): sco_py_amd/numdiff.py:_richardson
-__device__ __forceinline__ double richardson(double (&tab)[FD_LEVELS]) {
-  double p4 = 4.0;
-#pragma unroll
-  for (int i = 1; i < FD_LEVELS; i++) {
-    const double fac = 1.0 / (p4 - 1.0);
-#pragma unroll
-    for (int lv = FD_LEVELS - 1; lv >= i; lv--) tab[lv] = tab[lv] + (tab[lv] - tab[lv - 1]) * fac;
-    p4 *= 4.0;
-  }
-  return tab[FD_LEVELS - 1];
-}
-
-// smallest eigenvalue of the symmetric d x d matrix H (d <= 16) by cyclic Jacobi rotations on a private copy
-// (the reference calls scipy.linalg.eigvalsh, expr.py:145; oracle/sco_ref.py:min_eig_jacobi is this sweep)
-#define OBJ_DMAX 16
-#define SCO_STATE_MAX 32      // widest state of a constraint block of the program family (span x dof)
-__device__ double min_eig_jacobi(const double *H, int d) {
-  double A[OBJ_DMAX * OBJ_DMAX];
-  for (int i = 0; i < d * d; i++) A[i] = H[i];
-  for (int sweep = 0; sweep < 12; sweep++)
-    for (int p = 0; p < d - 1; p++)
-      for (int q = p + 1; q < d; q++) {
-        const double apq = A[p * d + q];
-        if (fabs(apq) < 1e-300) continue;
-        const double theta = (A[q * d + q] - A[p * d + p]) / (2.0 * apq);
-        // |theta| beyond 1e150 would overflow theta^2: there sqrt(theta^2 + 1) = |theta| to the last bit
-        const double at = fabs(theta);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (at + (at > 1e150 ? at : sqrt(theta * theta + 1.0)));
-        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-        for (int k = 0; k < d; k++) {            // columns p, q
-          const double rp = A[k * d + p], rq = A[k * d + q];
-          A[k * d + p] = c * rp - sn * rq; A[k * d + q] = sn * rp + c * rq;
-        }
-        for (int k = 0; k < d; k++) {            // rows p, q
-          const double rp = A[p * d + k], rq = A[q * d + k];
-          A[p * d + k] = c * rp - sn * rq; A[q * d + k] = sn * rp + c * rq;
-        }
-      }
-  double lam = A[0];
-  for (int i = 1; i < d; i++) lam = fmin(lam, A[i * d + i]);
-  return lam;
-}
-
-// Non-linear row e of a problem: hinge rows (timestep-major, R per timestep) first, then the NE
-// equality rows of the reach variant on the last timestep (constraint block index T).
-// `eq`: 0 hinge row, 1 equality row of the reach variant (block NBt = T on the last timestep, arm kinematics),
-// 2 equality row inside a block of the state families (the last Req rows of the block, r03)
-struct RowRef { int blk, t, r, eq; };
-struct RowLay { int T, NBt, R, Req; };
-__device__ __forceinline__ RowRef row_ref(int e, const RowLay &L) {
-  RowRef q;
-  if (e < L.NBt * L.R) { q.blk = e / L.R; q.t = q.blk; q.r = e % L.R; q.eq = (q.r >= L.R - L.Req) ? 2 : 0; }
-  else { q.blk = L.NBt; q.t = L.T - 1; q.r = e - L.NBt * L.R; q.eq = 1; }
-  return q;
-}
-
-struct RowCtx { const double *len, *obs, *target; const int *point_link; const double *point_frac; int d, O, point;
-                const double *qQ, *qa, *qc;         // SCO_FAM_STATE_QUADRATIC: this problem's row coefficients (point == 2)
-                const int *pw, *pptr; const double *pconst, *ppar; int par_step, R1; };   // SCO_FAM_STATE_PROGRAM (point == 3): words, row starts, constants, this problem's parameters (block t: ppar + t * par_step)
-// (for the state families `d` is the dimension of a BLOCK's state, span x dof)
-
-// SCO_FAM_STATE_PROGRAM: value of program `o` at th, up to two coordinates perturbed (finite differences)
-__device__ __forceinline__ double prog_eval(const RowCtx &c, const double *par, int o, const double *th, int pi, double hi, int pj, double hj) {
-  double st[SCO_PROGRAM_STACK];
-  int sp = 0;
-  for (int w = c.pptr[o];; w++) {
-    const int op = c.pw[2 * w], arg = c.pw[2 * w + 1];
-    if (op == SCO_OP_END) break;
-    switch (op) {
-      case SCO_OP_X: st[sp++] = th[arg] + (arg == pi ? hi : 0.0) + (arg == pj ? hj : 0.0); break;
-      case SCO_OP_P: st[sp++] = par[arg]; break;
-      case SCO_OP_C: st[sp++] = c.pconst[arg]; break;
-      case SCO_OP_ADD: sp--; st[sp - 1] = st[sp - 1] + st[sp]; break;
-      case SCO_OP_SUB: sp--; st[sp - 1] = st[sp - 1] - st[sp]; break;
-      case SCO_OP_MUL: sp--; st[sp - 1] = st[sp - 1] * st[sp]; break;
-      case SCO_OP_DIV: sp--; st[sp - 1] = st[sp - 1] / st[sp]; break;
-      case SCO_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
-      case SCO_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
-      case SCO_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
-      case SCO_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
-      case SCO_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
-      default: st[sp - 1] = st[sp - 1] * st[sp - 1]; break;       // SCO_OP_SQUARE
-    }
-  }
-  return st[0];
-}
-// d(program o) / d x_j by forward-mode differentiation: every stack slot carries (value, derivative along e_j); the rules,
-// in this order of operations, are the ones sco_py_amd/rowexpr.py:Program.jacobian applies on the host (the `grad` a caller
-// hands to the reference's Expr, expr.py:86-100), so host and device agree to rounding
-__device__ __forceinline__ double prog_dual(const RowCtx &c, const double *par, int o, const double *th, int j) {
-  // no fused multiply-adds here: the host applies the rules operation by operation (NumPy), and a derivative that differs in
-  // its last bit can move the iteration count of a slowly converging QP by many termination checks
-#pragma clang fp contract(off)
-  double sv[SCO_PROGRAM_STACK], sd[SCO_PROGRAM_STACK];
-  int sp = 0;
-  for (int w = c.pptr[o];; w++) {
-    const int op = c.pw[2 * w], arg = c.pw[2 * w + 1];
-    if (op == SCO_OP_END) break;
-    switch (op) {
-      case SCO_OP_X: sv[sp] = th[arg]; sd[sp++] = (arg == j) ? 1.0 : 0.0; break;
-      case SCO_OP_P: sv[sp] = par[arg]; sd[sp++] = 0.0; break;
-      case SCO_OP_C: sv[sp] = c.pconst[arg]; sd[sp++] = 0.0; break;
-      case SCO_OP_ADD: sp--; sv[sp - 1] = sv[sp - 1] + sv[sp]; sd[sp - 1] = sd[sp - 1] + sd[sp]; break;
-      case SCO_OP_SUB: sp--; sv[sp - 1] = sv[sp - 1] - sv[sp]; sd[sp - 1] = sd[sp - 1] - sd[sp]; break;
-      case SCO_OP_MUL: sp--; sd[sp - 1] = sd[sp - 1] * sv[sp] + sv[sp - 1] * sd[sp]; sv[sp - 1] = sv[sp - 1] * sv[sp]; break;
-      case SCO_OP_DIV: { sp--; const double qv = sv[sp - 1] / sv[sp]; sd[sp - 1] = (sd[sp - 1] - qv * sd[sp]) / sv[sp]; sv[sp - 1] = qv; break; }
-      case SCO_OP_NEG: sv[sp - 1] = -sv[sp - 1]; sd[sp - 1] = -sd[sp - 1]; break;
-      case SCO_OP_SIN: sd[sp - 1] = cos(sv[sp - 1]) * sd[sp - 1]; sv[sp - 1] = sin(sv[sp - 1]); break;
-      case SCO_OP_COS: sd[sp - 1] = -(sin(sv[sp - 1]) * sd[sp - 1]); sv[sp - 1] = cos(sv[sp - 1]); break;
-      case SCO_OP_SQRT: { const double r = sqrt(sv[sp - 1]); sd[sp - 1] = sd[sp - 1] / (2.0 * r); sv[sp - 1] = r; break; }
-      case SCO_OP_EXP: { const double ev = exp(sv[sp - 1]); sd[sp - 1] = ev * sd[sp - 1]; sv[sp - 1] = ev; break; }
-      default: sd[sp - 1] = (2.0 * sv[sp - 1]) * sd[sp - 1]; sv[sp - 1] = sv[sp - 1] * sv[sp - 1]; break;       // SCO_OP_SQUARE
-    }
-  }
-  return sd[0];
-}
-// f of row q at th (the raw function value: the right-hand side val is 0 for hinge rows and the equality rows of the state
-// families and target[r] for the reach rows and is applied by the callers, in the reference's order)
-__device__ __forceinline__ double row_value(const RowCtx &c, const RowRef &q, const double *th, int pert, double h) {
-  if (q.eq == 1) return arm_ee(th, c.len, c.d, q.r, pert, h);
-  const int kp = q.r / c.O, o = q.r % c.O;
-  if (c.point == 3) {                          // SCO_FAM_STATE_PROGRAM: the row's postfix program; r04: behind R1 circle rows of the point x[0:2]
-    if (q.r < c.R1) {
-      const double dx = th[0] + (pert == 0 ? h : 0.0) - c.obs[3 * q.r], dy = th[1] + (pert == 1 ? h : 0.0) - c.obs[3 * q.r + 1];
-      return c.obs[3 * q.r + 2] - sqrt(dx * dx + dy * dy);
-    }
-    return prog_eval(c, c.ppar + q.t * c.par_step, q.r - c.R1, th, pert, h, -1, 0.0);
-  }
-  if (c.point == 2) {                          // SCO_FAM_STATE_QUADRATIC: 1/2 x' Q x + a' x + c of row o
-    const double *Q = c.qQ + (size_t)o * c.d * c.d, *av = c.qa + (size_t)o * c.d;
-    double val = c.qc[o];
-    for (int i = 0; i < c.d; i++) {
-      const double xi = th[i] + (i == pert ? h : 0.0);
-      double qx = 0.0;
-      for (int j2 = 0; j2 < c.d; j2++) qx += Q[i * c.d + j2] * (th[j2] + (j2 == pert ? h : 0.0));
-      val += xi * (av[i] + 0.5 * qx);
-    }
-    return val;
-  }
-  if (c.point) {                               // SCO_FAM_POINT_CIRCLES: r_o - || x[0:2] - c_o ||
-    const double dx = th[0] + (pert == 0 ? h : 0.0) - c.obs[3 * o], dy = th[1] + (pert == 1 ? h : 0.0) - c.obs[3 * o + 1];
-    return c.obs[3 * o + 2] - sqrt(dx * dx + dy * dy);
-  }
-  return arm_row(th, c.len, c.point_link[kp], c.point_frac[kp], c.obs[3 * o], c.obs[3 * o + 1], c.obs[3 * o + 2], pert, h);
-}
-__device__ __forceinline__ double row_grad(const RowCtx &c, const RowRef &q, const double *th, int j) {
-  if (q.eq == 1) return arm_ee_grad(th, c.len, c.d, q.r, j);
-  const int kp = q.r / c.O, o = q.r % c.O;
-  if (c.point == 3) {                          // forward-mode differentiation of the row's program (r03); circle rows in closed form
-    if (q.r < c.R1) {
-      if (j > 1) return 0.0;
-      const double dx = th[0] - c.obs[3 * q.r], dy = th[1] - c.obs[3 * q.r + 1];
-      return -(j == 0 ? dx : dy) / sqrt(dx * dx + dy * dy);
-    }
-    return prog_dual(c, c.ppar + q.t * c.par_step, q.r - c.R1, th, j);
-  }
-  if (c.point == 2) {                          // a_j + sum_i Q_ji x_i  (Q symmetric)
-    const double *Q = c.qQ + (size_t)o * c.d * c.d;
-    double g = c.qa[(size_t)o * c.d + j];
-    for (int i = 0; i < c.d; i++) g += Q[j * c.d + i] * th[i];
-    return g;
-  }
-  if (c.point) {
-    if (j > 1) return 0.0;
-    const double dx = th[0] - c.obs[3 * o], dy = th[1] - c.obs[3 * o + 1];
-    return -(j == 0 ? dx : dy) / sqrt(dx * dx + dy * dy);
-  }
-  return arm_row_grad(th, c.len, c.point_link[kp], c.point_frac[kp], c.obs[3 * o], c.obs[3 * o + 1], j);
-}
-// non-quadratic objective term of a timestep with up to two perturbed coordinates: the arm's end-effector term
-// (SCO_FAM_FLAG_EE_COST) or the objective program (SCO_FAM_FLAG_OBJ_PROGRAM / SCO_FAM_FLAG_OBJ_BLOCK: program index O; for a
-// block term `t` is the block and th its span * dof state)
-struct ObjCtx { int kind; const double *len; int d; double tx, ty, w; };
-__device__ __forceinline__ double obj_value(const ObjCtx &oc, const RowCtx &c, int t, const double *th, int pi, double hi, int pj, double hj) {
-  if (oc.kind >= 2) return prog_eval(c, c.ppar + t * c.par_step, c.O - c.R1, th, pi, hi, pj, hj);
-  return arm_ee_cost(th, oc.len, oc.d, oc.tx, oc.ty, oc.w, pi, hi, pj, hj);
-}
-__device__ __forceinline__ double row_rhs(const RowCtx &c, const RowRef &q) { return q.eq == 1 ? c.target[q.r] : 0.0; }
-// violation of a row with value g = f - val: |g| for equality rows, max(g, 0) for hinge rows (prob.py:582-590)
-__device__ __forceinline__ double row_viol(const RowRef &q, double g) { return q.eq ? fabs(g) : fmax(g, 0.0); }
 
 // index of the stored point whose rounded key equals that of x (d coordinates), or -1
 __device__ __forceinline__ int memo_find(const double *keys, int count, int d, const double *x) {
@@ -513,6 +255,89 @@ __device__ __forceinline__ double lin_ineq_hi(const SqpDev &s, int b, int i) {
   const int k = v - s.m_vel;
   return k < s.n_x ? s.jhi[(size_t)b * s.d + k % s.d] : -s.jlo[(size_t)b * s.d + (k - s.n_x) % s.d];
 }
+// bounds of linear row i < m_lin, the same in both QPs: the pins, then the inequality rows
+__device__ __forceinline__ void lin_row_bounds(const SqpDev &s, int b, int i, double *lo, double *hi) {
+  if (i < s.d) *lo = *hi = s.start[(size_t)b * s.d + i];
+  else if (i < s.m_pin) *lo = *hi = s.goal[(size_t)b * s.d + (i - s.d)];
+  else { *hi = lin_ineq_hi(s, b, i); *lo = lin_row_is_eq(s, i) ? *hi : -INFINITY; }
+}
+
+// what the row and objective models (sqp_rows.h) need of problem b
+__device__ __forceinline__ RowCtx row_ctx(const SqpDev &s, int b) {
+  return RowCtx{s.link_len + (size_t)b * s.d, s.obstacles + (size_t)b * s.O * 3, s.target + (size_t)b * 2, s.point_link, s.point_frac,
+                s.ds, s.O, s.point,
+                s.qQ + (size_t)b * s.O * s.ds * s.ds, s.qa + (size_t)b * s.O * s.ds, s.qc + (size_t)b * s.O,
+                s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1};
+}
+__device__ __forceinline__ ObjCtx obj_ctx(const SqpDev &s, int b) {
+  return ObjCtx{s.cost, s.link_len + (size_t)b * s.d, s.d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]};
+}
+
+// Q3 emulation.  A history holds, per constraint block, up to H rounded points (keys, ds numbers each) and how many
+// (count).  memo_lookup: hit[t] = the stored point block t's state at x rounds onto, or -1 (always -1 without `memo`).
+// Block NBt (the reach equality rows) lives on the last timestep.
+__device__ __forceinline__ void memo_lookup(const SqpDev &s, bool memo, const double *keys, const int *count, int H, const double *x,
+                                            int *hit) {
+  for (int t = threadIdx.x; t < s.NB; t += SCO_BLOCK)
+    hit[t] = memo ? memo_find(keys + (size_t)t * H * s.ds, count[t], s.ds, x + (t < s.NBt ? t : s.T - 1) * s.d) : -1;
+}
+// memo_commit: every block that missed gets its key stored and its counter bumped -- after all its values have been
+// written -- or, when its history is full, raises SCO_SQP_FLAG_MEMO_FULL
+__device__ __forceinline__ void memo_commit(const SqpDev &s, SqpScalars &sc, double *keys, int *count, int H, const double *x,
+                                            const int *hit) {
+  for (int t = threadIdx.x; t < s.NB; t += SCO_BLOCK) {
+    if (hit[t] >= 0) continue;
+    if (count[t] < H) {
+      const double *xb = x + (t < s.NBt ? t : s.T - 1) * s.d;
+      for (int j = 0; j < s.ds; j++) keys[((size_t)t * H + count[t]) * s.ds + j] = rint(xb[j] * 1e6);
+      count[t] += 1;
+    } else atomicOr(&sc.flags, SCO_SQP_FLAG_MEMO_FULL);
+  }
+}
+
+// d f / d x_j by central differences on a halving ladder + Richardson extrapolation (expr.py:61-69, numdiff.py);
+// f(j, h) = the function with coordinate j moved by h, xj = that coordinate
+template <typename F>
+__device__ __forceinline__ double central_diff(double xj, int j, F f) {
+  const double h0 = FD_BASE * fmax(1.0, fabs(xj));
+  double tab[FD_LEVELS];
+#pragma unroll
+  for (int lv = 0; lv < FD_LEVELS; lv++) {
+    const double h = h0 / (double)(1 << lv);
+    const double fp = f(j, h);
+    const double fm = f(j, -h);
+    tab[lv] = (fp - fm) / (2.0 * h);
+  }
+  return richardson(tab);
+}
+
+// row e of the affine model applied to x: sum_j J[e][j] x[q.t d + j] in j order (a reach row lives on one timestep)
+__device__ __forceinline__ double model_row(const double *J, const double *x, const RowRef &q, int e, int d, int ds) {
+  const int nj = q.eq == ROW_REACH_EQ ? d : ds;
+  double acc = 0.0;
+  for (int j = 0; j < nj; j++) acc += J[(size_t)e * ds + j] * x[q.t * d + j];
+  return acc;
+}
+
+// get_value(vectorize=True) (prob.py:558-570): per-block sums of what a row contributes, viol(e, q), then per-group sums
+// in block order, handed to out(g, sum)
+template <typename F, typename G>
+__device__ __forceinline__ void group_sums(const SqpDev &s, const RowLay &L, F viol, G out) {
+  __shared__ double bsum[260];
+  for (int blk = threadIdx.x; blk < s.NB; blk += SCO_BLOCK) {
+    const int e0 = blk < s.NBt ? blk * s.R : s.NBt * s.R, cnt = blk < s.NBt ? s.R : s.NE;
+    double acc = 0.0;
+    for (int e = e0; e < e0 + cnt; e++) acc += viol(e, row_ref(e, L));
+    bsum[blk] = acc;
+  }
+  __syncthreads();
+  for (int g = threadIdx.x; g < s.G; g += SCO_BLOCK) {
+    double acc = 0.0;
+    for (int blk = 0; blk < s.NB; blk++) if ((s.gmask[blk] >> g) & 1u) acc += bsum[blk];
+    out(g, acc);
+  }
+  __syncthreads();
+}
 
 // --------------------------------------------------------------------------
 // round 0: projection QP values  (prob.py:369-412)
@@ -541,9 +366,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_assemble_kernel(SqpDev s, 
   }
   for (int i = tid; i < m0; i += SCO_BLOCK) {
     double lo, hi;
-    if (i < d) lo = hi = s.start[(size_t)b * d + i];
-    else if (i < s.m_pin) lo = hi = s.goal[(size_t)b * d + (i - d)];
-    else if (i < s.m_lin) { hi = lin_ineq_hi(s, b, i); lo = lin_row_is_eq(s, i) ? hi : -INFINITY; }
+    if (i < s.m_lin) lin_row_bounds(s, b, i, &lo, &hi);
     else { lo = -INFINITY; hi = INFINITY; }
     q0.l[(size_t)b * m0 + i] = lo; q0.u[(size_t)b * m0 + i] = hi;
     q0.w[(size_t)b * m0 + i] = 1;
@@ -593,7 +416,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_post_kernel(SqpDev s, QpDe
         const int t = col / d;
         const double wj = s.objw ? s.objw[(size_t)b * d + col % d] : 1.0;
         const double aj = s.accw ? s.accw[(size_t)b * d + col % d] : 0.0;
-        if (s.cost == 3) {                    // block terms: the dense band of rows max(0, t - S + 1) d .. col
+        if (s.cost == OBJ_BLOCK) {                    // block terms: the dense band of rows max(0, t - S + 1) d .. col
           if (s.acc && s.S == 2 && t > 1) Pv[pos++] = 2.0 * aj;
           for (int r = (t - s.S + 1 > 0 ? t - s.S + 1 : 0) * d; r <= col; r++)
             Pv[pos++] = r == col ? obj_p_diag(t, s.T, wj, aj) : r == col - d ? obj_p_off1(t, s.T, wj, aj) :
@@ -620,12 +443,10 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_post_kernel(SqpDev s, QpDe
     int *w = q1.w + (size_t)b * m;
     for (int i = tid; i < m; i += SCO_BLOCK) {
       double lo, hi;
-      if (i < d) lo = hi = s.start[(size_t)b * d + i];
-      else if (i < s.m_pin) lo = hi = s.goal[(size_t)b * d + (i - d)];
-      else if (i < s.m_lin) { hi = lin_ineq_hi(s, b, i); lo = lin_row_is_eq(s, i) ? hi : -INFINITY; }
+      if (i < s.m_lin) lin_row_bounds(s, b, i, &lo, &hi);
       else if (i < s.m_lin + s.m_nl) {                                  // hinge rows; equality rows are set by convexify
         const RowRef qr = row_ref(i - s.m_lin, RowLay{s.T, s.NBt, s.R, s.Req});
-        lo = qr.eq ? 0.0 : -INFINITY; hi = 0.0;
+        lo = qr.eq != ROW_HINGE ? 0.0 : -INFINITY; hi = 0.0;
       }
       else if (i < s.m_lin + s.m_nl + n_x) { lo = -INFINITY; hi = INFINITY; }
       else { lo = 0.0; hi = INFINITY; }
@@ -725,13 +546,11 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
   if (state == ST_DONE || parked) return;
   __shared__ double red[NWAVE * 4];
   __shared__ double of0[260];           // f of the non-quadratic objective terms at the convexification point
-  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, O = s.O, n = s.n, m = s.m;
+  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, n = s.n, m = s.m;
   const int ds = s.ds, NBt = s.NBt;             // state dimension of a block, number of timestep blocks
-  const int NO = s.cost == 3 ? NBt : T;         // objective terms: one per timestep, or one per block (cost 3)
+  const int NO = s.cost == OBJ_BLOCK ? NBt : T;         // objective terms: one per timestep, or one per block (OBJ_BLOCK)
   const RowLay L{T, NBt, R, s.Req};
   double *x = s.x + (size_t)b * n_x, *xs = s.x_saved + (size_t)b * n_x;
-  const double *len = s.link_len + (size_t)b * d;
-  const double *obs = s.obstacles + (size_t)b * O * 3;
   double *gs = s.gsave + (size_t)b * s.m_nl, *J = s.J + (size_t)b * s.m_nl * ds, *bm = s.bmod + (size_t)b * s.m_nl;
   unsigned char *mask = s.mask + (size_t)b * s.m_nl * ds;
   const double penalty = sc.penalty, trust = sc.trust;
@@ -743,17 +562,12 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
     // Q3: which blocks sit on an already-seen / already-convexified rounded point
     __shared__ int ev_hit[260], cv_hit[260];
     const int H = s.H, HC = s.HC, NB = s.NB, RM = s.RM, m_nl = s.m_nl;
-    const RowCtx rc{len, obs, s.target + (size_t)b * 2, s.point_link, s.point_frac, ds, O, s.point,
-                  s.qQ + (size_t)b * O * ds * ds, s.qa + (size_t)b * O * ds, s.qc + (size_t)b * O,
-                  s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1};
+    const RowCtx rc = row_ctx(s, b);
     double *hkey = s.hkey + (size_t)b * NB * H * ds, *hval = s.hval + (size_t)b * NB * H * RM;
     double *ckey = s.ckey + (size_t)b * NB * HC * ds, *cJ = s.cJ + (size_t)b * NB * HC * RM * ds, *cb = s.cb + (size_t)b * NB * HC * RM;
     int *hn = s.hn + (size_t)b * NB, *cn = s.cn + (size_t)b * NB;
-    for (int t = tid; t < NB; t += SCO_BLOCK) {
-      const double *xb = x + (t < NBt ? t : T - 1) * d;    // block NBt (reach equality rows) lives on the last timestep
-      ev_hit[t] = p.memo ? memo_find(hkey + (size_t)t * H * ds, hn[t], ds, xb) : -1;
-      cv_hit[t] = p.memo ? memo_find(ckey + (size_t)t * HC * ds, cn[t], ds, xb) : -1;
-    }
+    memo_lookup(s, p.memo, hkey, hn, H, x, ev_hit);
+    memo_lookup(s, p.memo, ckey, cn, HC, x, cv_hit);
     __syncthreads();
     // S1: f(x) per row, memoised on the rounded point (expr.py:34-41)
     for (int e = tid; e < m_nl; e += SCO_BLOCK) {
@@ -773,32 +587,14 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
       const RowRef q = row_ref(e / ds, L);
       const double *th = x + q.t * d;
       double val;
-      if (q.eq == 1 && j >= d) {
+      if (q.eq == ROW_REACH_EQ && j >= d) {
         val = 0.0;                               // (a reach row lives on ONE timestep; its entry slots beyond dof do not exist)
       } else if (cv_hit[q.blk] >= 0) {
         val = cJ[(((size_t)q.blk * HC + cv_hit[q.blk]) * RM + q.r) * ds + j];
       } else if (s.analytic_jac) {
         val = row_grad(rc, q, th, j);
       } else {
-        // central differences on a halving ladder + Richardson extrapolation
-        const double h0 = FD_BASE * fmax(1.0, fabs(th[j]));
-        double tab[FD_LEVELS];
-#pragma unroll
-        for (int lv = 0; lv < FD_LEVELS; lv++) {
-          const double h = h0 / (double)(1 << lv);
-          const double fp = row_value(rc, q, th, j, h);
-          const double fm = row_value(rc, q, th, j, -h);
-          tab[lv] = (fp - fm) / (2.0 * h);
-        }
-        double p4 = 4.0;
-#pragma unroll
-        for (int i = 1; i < FD_LEVELS; i++) {
-          const double fac = 1.0 / (p4 - 1.0);
-#pragma unroll
-          for (int lv = FD_LEVELS - 1; lv >= i; lv--) tab[lv] = tab[lv] + (tab[lv] - tab[lv - 1]) * fac;
-          p4 *= 4.0;
-        }
-        val = tab[FD_LEVELS - 1];
+        val = central_diff(th[j], j, [&](int jj, double h) { return row_value(rc, q, th, jj, h); });
       }
       J[e] = val;
       if (p.memo && cv_hit[q.blk] < 0 && cn[q.blk] < HC) cJ[(((size_t)q.blk * HC + cn[q.blk]) * RM + q.r) * ds + j] = val;
@@ -813,34 +609,31 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
     int *w = q1.w + (size_t)b * m;
     for (int e = tid; e < m_nl; e += SCO_BLOCK) {
       const RowRef q = row_ref(e, L);
-      const int nj = q.eq == 1 ? d : ds;
-      double acc = 0.0;
-      for (int j = 0; j < nj; j++) acc += J[(size_t)e * ds + j] * x[q.t * d + j];
-      double bb = (gs[e] - acc) - row_rhs(rc, q);
+      double bb = (gs[e] - model_row(J, x, q, e, d, ds)) - row_rhs(rc, q);
       if (cv_hit[q.blk] >= 0) bb = cb[((size_t)q.blk * HC + cv_hit[q.blk]) * RM + q.r];
       else if (p.memo && cn[q.blk] < HC) cb[((size_t)q.blk * HC + cn[q.blk]) * RM + q.r] = bb;
       bm[e] = bb;
       u[s.m_lin + e] = -bb;            // hinge: -inf <= a x - t <= -b  (prob.py:265-275, 486)
-      if (q.eq) l[s.m_lin + e] = -bb;  // abs:   a x - p + n = -b        (prob.py:303-312, 480-484)
+      if (q.eq != ROW_HINGE) l[s.m_lin + e] = -bb;  // abs:   a x - p + n = -b        (prob.py:303-312, 480-484)
       w[s.m_lin + e] = k_rows;         // row present k times (prob.py:508-509)
     }
     for (int e = tid; e < m_nl * ds; e += SCO_BLOCK) {
       const int j = e % ds;
       const RowRef q = row_ref(e / ds, L);
-      if (q.eq == 1 && j >= d) continue;
+      if (q.eq == ROW_REACH_EQ && j >= d) continue;
       // column c = (timestep q.t + j / d, coordinate j % d) holds, below its linear entries, the R slots of every block
       // that covers its timestep, in block order (sco_sqp_create)
       const int c = q.t * d + j, tfirst = (c / d - s.S + 1 > 0) ? c / d - s.S + 1 : 0;
-      const int pos = q.eq == 1 ? s.epos[j] + q.r : s.jpos[c] + (q.blk - tfirst) * R + q.r;
+      const int pos = q.eq == ROW_REACH_EQ ? s.epos[j] + q.r : s.jpos[c] + (q.blk - tfirst) * R + q.r;
       Av[pos] = mask[e] ? J[e] : 0.0;   // prob.py:493-504
     }
     double *qv = q1.q + (size_t)b * n;
     for (int i = tid; i < s.n_slack; i += SCO_BLOCK) qv[n_x + i] = slack_cost;   // prob.py:424-426
     if (s.cost) {
       // ---- non-quadratic objective terms: Expr.convexify(degree 2) (expr.py:143-153) per timestep block, or per constraint
-      // block of S timesteps (cost 3: NO = NBt terms on dO = ds numbers; block t's state starts at x[t d] as well)
-      const ObjCtx oc{s.cost, len, d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]};
-      const int dO = s.cost == 3 ? ds : d;
+      // block of S timesteps (OBJ_BLOCK: NO = NBt terms on dO = ds numbers; block t's state starts at x[t d] as well)
+      const ObjCtx oc = obj_ctx(s, b);
+      const int dO = s.cost == OBJ_BLOCK ? ds : d;
       double *oH = s.oH + (size_t)b * NO * dO * dO, *oA = s.oA + (size_t)b * NO * dO, *ob = s.ob + (size_t)b * NO;
       // f(x), memoised on the rounded point like every Expr.eval (expr.py:34-41); the term shares the point history of
       // its constraint block (same Variable, same evaluation points): its value is the block's last column
@@ -886,14 +679,7 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
       for (int e = tid; e < NO * dO; e += SCO_BLOCK) {
         const int t = e / dO, j = e % dO;
         const double *th = x + t * d;
-        const double h0 = FD_BASE * fmax(1.0, fabs(th[j]));
-        double tab[FD_LEVELS];
-#pragma unroll
-        for (int lv = 0; lv < FD_LEVELS; lv++) {
-          const double h = h0 / (double)(1 << lv);
-          tab[lv] = (obj_value(oc, rc, t, th, j, h, -1, 0.0) - obj_value(oc, rc, t, th, j, -h, -1, 0.0)) / (2.0 * h);
-        }
-        oA[e] = richardson(tab);
+        oA[e] = central_diff(th[j], j, [&](int jj, double h) { return obj_value(oc, rc, t, th, jj, h, -1, 0.0); });
       }
       __syncthreads();
       // eigenvalue shift, then Q = H, A = g - x'H, b = 1/2 x'Hx - g.x + f (expr.py:145-152)
@@ -917,7 +703,7 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
       __syncthreads();
       // QuadExpr lowering (prob.py:348-367; osqp_utils.py:153-163): Q into the upper triangle of P, A into q
       double *Pv = q1.Pval + (size_t)b * q1.nnzP;
-      if (s.cost == 3) {
+      if (s.cost == OBJ_BLOCK) {
         // blocks overlap: every entry of the band is written by one thread, which adds, in the reference's order, the
         // smoothing QuadExpr first, then each covering block's Q in block order -- an off-diagonal pair as its two halves
         // 0.5 Q_ij + 0.5 Q_ji, the diagonal whole (osqp_utils.py:153-163); q likewise (osqp_utils.py:146-148)
@@ -961,36 +747,16 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
     }
     block_reduce_sm<2, 0>(v, red);
     if (s.G > 0) {
-      // get_value(vectorize=True): per-block sums, then per-group sums in block order (prob.py:558-570)
-      __shared__ double bsum[260];
-      for (int blk = tid; blk < NB; blk += SCO_BLOCK) {
-        const int e0 = blk < NBt ? blk * R : NBt * R, cnt = blk < NBt ? R : s.NE;
-        double acc = 0.0;
-        for (int e = e0; e < e0 + cnt; e++) { const RowRef q = row_ref(e, L); acc += row_viol(q, gs[e] - row_rhs(rc, q)); }
-        bsum[blk] = acc;
-      }
-      __syncthreads();
-      for (int g = tid; g < s.G; g += SCO_BLOCK) {
-        double acc = 0.0;
-        for (int blk = 0; blk < NB; blk++) if ((s.gmask[blk] >> g) & 1u) acc += bsum[blk];
-        s.mvec[(size_t)b * 32 + g] = acc;
-      }
-      __syncthreads();
+      // per-group violation at the saved point
+      group_sums(s, L, [&](int e, const RowRef &q) { return row_viol(q, gs[e] - row_rhs(rc, q)); },
+                 [&](int g, double sum) { s.mvec[(size_t)b * 32 + g] = sum; });
     }
     for (int i = tid; i < n_x; i += SCO_BLOCK) xs[i] = x[i];
     // commit the new history entries (keys last, after every value has been written)
-    if (p.memo)
-      for (int t = tid; t < NB; t += SCO_BLOCK) {
-        const double *xb = x + (t < NBt ? t : T - 1) * d;
-        if (ev_hit[t] < 0 && hn[t] < H) {
-          for (int j = 0; j < ds; j++) hkey[((size_t)t * H + hn[t]) * ds + j] = rint(xb[j] * 1e6);
-          hn[t] += 1;
-        } else if (ev_hit[t] < 0) atomicOr(&sc.flags, SCO_SQP_FLAG_MEMO_FULL);
-        if (cv_hit[t] < 0 && cn[t] < HC) {
-          for (int j = 0; j < ds; j++) ckey[((size_t)t * HC + cn[t]) * ds + j] = rint(xb[j] * 1e6);
-          cn[t] += 1;
-        } else if (cv_hit[t] < 0) atomicOr(&sc.flags, SCO_SQP_FLAG_MEMO_FULL);
-      }
+    if (p.memo) {
+      memo_commit(s, sc, hkey, hn, H, x, ev_hit);
+      memo_commit(s, sc, ckey, cn, HC, x, cv_hit);
+    }
     if (tid == 0) {
       sc.merit_viol = v[1];
       sc.merit = v[0] + penalty * v[1];
@@ -1025,12 +791,10 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
     return;
   }
   __shared__ double red[NWAVE * 6];
-  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, O = s.O, n = s.n;
+  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, n = s.n;
   const int ds = s.ds, NBt = s.NBt;
   const RowLay L{T, NBt, R, s.Req};
   double *x = s.x + (size_t)b * n_x, *xs = s.x_saved + (size_t)b * n_x;
-  const double *len = s.link_len + (size_t)b * d;
-  const double *obs = s.obstacles + (size_t)b * O * 3;
   const double *gs = s.gsave + (size_t)b * s.m_nl, *J = s.J + (size_t)b * s.m_nl * ds, *bm = s.bmod + (size_t)b * s.m_nl;
   const int status = q1.status[b], iters = q1.iters[b];
   // every scalar is read BEFORE the reduction's barriers; thread 0 rewrites them afterwards
@@ -1041,20 +805,17 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
   // Q3: blocks of the trial point that round onto an already-seen point reuse its f values
   __shared__ int ev_hit[260];
   const int H = s.H, NB = s.NB, RM = s.RM, m_nl = s.m_nl;
-  const RowCtx rc{len, obs, s.target + (size_t)b * 2, s.point_link, s.point_frac, ds, O, s.point,
-                  s.qQ + (size_t)b * O * ds * ds, s.qa + (size_t)b * O * ds, s.qc + (size_t)b * O,
-                  s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1};
+  const RowCtx rc = row_ctx(s, b);
   double *hkey = s.hkey + (size_t)b * NB * H * ds, *hval = s.hval + (size_t)b * NB * H * RM;
   int *hn = s.hn + (size_t)b * NB;
-  for (int t = tid; t < NB; t += SCO_BLOCK)
-    ev_hit[t] = p.memo ? memo_find(hkey + (size_t)t * H * ds, hn[t], ds, xq + (t < NBt ? t : T - 1) * d) : -1;
+  memo_lookup(s, p.memo, hkey, hn, H, xq, ev_hit);
   __syncthreads();
   // model violation uses the FULL Jacobian (prob.py:627-628), new violation f at the new point (prob.py:575-577)
   // v: quadratic objective, model violation, new violation, objective MODELS at the new point (prob.py:625-626),
   //    objective terms at the new point (prob.py:571-573), max violation at the saved point
   double v[6] = {traj_obj_partial(xq, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr), 0.0, 0.0, 0.0, 0.0, 0.0};
   if (s.cost) {
-    const int NO = s.cost == 3 ? NBt : T, dO = s.cost == 3 ? ds : d;     // per timestep, or per block (cost 3)
+    const int NO = s.cost == OBJ_BLOCK ? NBt : T, dO = s.cost == OBJ_BLOCK ? ds : d;     // per timestep, or per block (OBJ_BLOCK)
     const double *oH = s.oH + (size_t)b * NO * dO * dO, *oA = s.oA + (size_t)b * NO * dO, *ob = s.ob + (size_t)b * NO;
     for (int t = tid; t < NO; t += SCO_BLOCK) {
       const double *th = xq + t * d, *Ht = oH + (size_t)t * dO * dO;
@@ -1068,7 +829,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
       double f;
       if (ev_hit[t] >= 0) f = hval[((size_t)t * H + ev_hit[t]) * RM + (RM - 1)];
       else {
-        f = obj_value(ObjCtx{s.cost, len, d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]}, rc, t, th, -1, 0.0, -1, 0.0);
+        f = obj_value(obj_ctx(s, b), rc, t, th, -1, 0.0, -1, 0.0);
         if (p.memo && hn[t] < H) hval[((size_t)t * H + hn[t]) * RM + (RM - 1)] = f;
       }
       v[4] += f;
@@ -1077,10 +838,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
   for (int e = tid; e < m_nl; e += SCO_BLOCK) {
     const RowRef q = row_ref(e, L);
     const double rhs = row_rhs(rc, q);
-    const int nj = q.eq == 1 ? d : ds;
-    double acc = 0.0;
-    for (int j = 0; j < nj; j++) acc += J[(size_t)e * ds + j] * xq[q.t * d + j];
-    v[1] += row_viol(q, acc + bm[e]);
+    v[1] += row_viol(q, model_row(J, xq, q, e, d, ds) + bm[e]);
     double g;
     if (ev_hit[q.blk] >= 0) g = hval[((size_t)q.blk * H + ev_hit[q.blk]) * RM + q.r];
     else {
@@ -1091,42 +849,16 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
     v[5] = fmax(v[5], row_viol(q, gs[e] - rhs));                 // max violation at the SAVED point
   }
   __syncthreads();
-  if (p.memo) {
-    for (int t = tid; t < NB; t += SCO_BLOCK) {
-      if (ev_hit[t] < 0 && hn[t] < H) {
-        const double *xb = xq + (t < NBt ? t : T - 1) * d;
-        for (int j = 0; j < ds; j++) hkey[((size_t)t * H + hn[t]) * ds + j] = rint(xb[j] * 1e6);
-        hn[t] += 1;
-      } else if (ev_hit[t] < 0) {
-        atomicOr(&sc.flags, SCO_SQP_FLAG_MEMO_FULL);
-      }
-    }
-  }
+  if (p.memo) memo_commit(s, sc, hkey, hn, H, xq, ev_hit);
   block_reduce_sm<5, 1>(v, red);
   // constraint groups: which violated groups stopped improving, and do their overlapping groups too
   // (solver.py:155-161, 209-235)
   __shared__ unsigned int g_stalled, g_report;
   if (s.G > 0) {
-    __shared__ double bsum[260], gimp[32];
-    for (int blk = tid; blk < NB; blk += SCO_BLOCK) {
-      const int e0 = blk < NBt ? blk * R : NBt * R, cnt = blk < NBt ? R : s.NE;
-      double acc = 0.0;
-      for (int e = e0; e < e0 + cnt; e++) {
-        const RowRef q = row_ref(e, L);
-        const int nj = q.eq == 1 ? d : ds;
-        double ax = 0.0;
-        for (int j = 0; j < nj; j++) ax += J[(size_t)e * ds + j] * xq[q.t * d + j];
-        acc += row_viol(q, ax + bm[e]);
-      }
-      bsum[blk] = acc;
-    }
-    __syncthreads();
-    for (int g = tid; g < s.G; g += SCO_BLOCK) {
-      double acc = 0.0;
-      for (int blk = 0; blk < NB; blk++) if ((s.gmask[blk] >> g) & 1u) acc += bsum[blk];
-      gimp[g] = s.mvec[(size_t)b * 32 + g] - acc;         // approx_improve_vec
-    }
-    __syncthreads();
+    __shared__ double gimp[32];
+    // per-group model violation at the trial point -> approx_improve_vec
+    group_sums(s, L, [&](int e, const RowRef &q) { return row_viol(q, model_row(J, xq, q, e, d, ds) + bm[e]); },
+               [&](int g, double sum) { gimp[g] = s.mvec[(size_t)b * 32 + g] - sum; });
     if (tid == 0) {
       unsigned int stalled = 0, report = 0;
       for (int g = 0; g < s.G; g++) {
@@ -1199,18 +931,14 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
 __global__ __launch_bounds__(SCO_BLOCK) void sqp_final_kernel(SqpDev s, double *merit_out, double *viol_out) {
   const int b = blockIdx.x, tid = threadIdx.x;
   __shared__ double red[NWAVE * 4];
-  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R, O = s.O;
+  const int n_x = s.n_x, d = s.d, T = s.T, R = s.R;
   const double *x = s.x + (size_t)b * n_x;
-  const double *len = s.link_len + (size_t)b * d;
-  const double *obs = s.obstacles + (size_t)b * O * 3;
-  const RowCtx rc{len, obs, s.target + (size_t)b * 2, s.point_link, s.point_frac, s.ds, O, s.point,
-                  s.qQ + (size_t)b * O * s.ds * s.ds, s.qa + (size_t)b * O * s.ds, s.qc + (size_t)b * O,
-                  s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1};
+  const RowCtx rc = row_ctx(s, b);
   const RowLay L{T, s.NBt, R, s.Req};
   double v[3] = {traj_obj_partial(x, d, T, tid, s.objw ? s.objw + (size_t)b * d : nullptr, s.accw ? s.accw + (size_t)b * d : nullptr), 0.0, 0.0};
   if (s.cost)
-    for (int t = tid; t < (s.cost == 3 ? s.NBt : T); t += SCO_BLOCK)
-      v[0] += obj_value(ObjCtx{s.cost, len, d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]}, rc, t, x + t * d, -1, 0.0, -1, 0.0);
+    for (int t = tid; t < (s.cost == OBJ_BLOCK ? s.NBt : T); t += SCO_BLOCK)
+      v[0] += obj_value(obj_ctx(s, b), rc, t, x + t * d, -1, 0.0, -1, 0.0);
   for (int e = tid; e < s.m_nl; e += SCO_BLOCK) {
     const RowRef q = row_ref(e, L);
     const double g = row_viol(q, row_value(rc, q, x + q.t * d, -1, 0.0) - row_rhs(rc, q));
@@ -1242,54 +970,28 @@ static int sq_alloc(sco_sqp *h, size_t count, T **out) {
   *out = (T *)p;
   return SCO_OK;
 }
+// allocate and upload this vector
+template <typename T>
+static int sq_upload(sco_sqp *h, const std::vector<T> &v, const T **out) {
+  T *p = nullptr;
+  if (int rc = sq_alloc(h, v.size(), &p)) return rc;
+  if (!v.empty()) SCO_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = p;
+  return SCO_OK;
+}
 
-static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc);
+static int sqp_create_impl(sco_sqp *h, int device, const SqpLayout &L);
 
 // r04: sco_sqp_create with n_rows GENERAL affine rows over the trajectory variables behind the built-in linear rows -- what a
 // caller of the reference adds with prob.add_cnt_expr(BoundExpr(EqExpr / LEqExpr(AffExpr(A, b), val), traj)) (prob.py:126-131,
 // 317-346): a shared CSR pattern (row_ptr[n_rows + 1], col_idx strictly increasing inside a row, columns = name-sorted
 // trajectory atoms t * dof + j), row_is_eq[r] != 0: a x = rhs, else a x <= rhs; coefficients and right-hand sides per problem
-// through sco_sqp_load_linear_rows.
+// through sco_sqp_load_linear_rows.  Which descriptors and patterns are accepted: sqp_check_desc (sqp_layout.cpp).
 extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int n_rows, const int *row_ptr, const int *col_idx,
                                    const int *row_is_eq, sco_sqp **out) {
   if (!desc || !out) { sco_set_error("sco_sqp_create: null pointer"); return SCO_ERR_ARG; }
-  if (n_rows < 0 || n_rows > 65536 || (n_rows > 0 && (!row_ptr || !col_idx || !row_is_eq))) { sco_set_error("sco_sqp_create_rows: bad row pattern"); return SCO_ERR_ARG; }
-  if (n_rows > 0) {
-    if (row_ptr[0] != 0) { sco_set_error("sco_sqp_create_rows: bad row pattern"); return SCO_ERR_ARG; }
-    const long long nx = (long long)desc->dof * desc->horizon;
-    for (int r = 0; r < n_rows; r++) {
-      if (row_ptr[r + 1] <= row_ptr[r] || row_ptr[r + 1] - row_ptr[r] > nx) { sco_set_error("sco_sqp_create_rows: bad row pattern (empty row or row_ptr not increasing)"); return SCO_ERR_ARG; }
-      for (int k = row_ptr[r]; k < row_ptr[r + 1]; k++)
-        if (col_idx[k] < 0 || col_idx[k] >= nx || (k > row_ptr[r] && col_idx[k] <= col_idx[k - 1])) {
-          sco_set_error("sco_sqp_create_rows: column indices must lie in [0, dof * horizon) and increase inside a row"); return SCO_ERR_ARG;
-        }
-    }
-  }
-  const int fam = desc->family & 15, span = desc->span > 0 ? desc->span : 1;
-  const bool statefam = fam == SCO_FAM_STATE_QUADRATIC || fam == SCO_FAM_STATE_PROGRAM;
-  // widest objective term: the per-thread eigenvalue sweep's, or with SCO_FAM_FLAG_OBJ_WIDE the wavefront's
-  const bool objwide = (desc->family & SCO_FAM_FLAG_OBJ_WIDE) != 0;
-  const int objmax = objwide ? SCO_STATE_MAX : OBJ_DMAX;
-  if (desc->batch <= 0 || desc->dof <= 0 || desc->horizon < 2 || desc->n_points <= 0 || desc->n_obstacles <= 0 ||
-      desc->horizon > 256 || (desc->family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_ACC_COST | SCO_FAM_FLAG_OBJ_BLOCK | SCO_FAM_FLAG_OBJ_WIDE)) ||
-      ((desc->family & SCO_FAM_FLAG_EE_COST) && desc->dof > OBJ_DMAX) || ((desc->family & SCO_FAM_FLAG_ACC_COST) && desc->horizon < 3) ||
-      (fam != SCO_FAM_ARM_CIRCLES && fam != SCO_FAM_ARM_REACH && fam != SCO_FAM_POINT_CIRCLES && !statefam) ||
-      (fam == SCO_FAM_POINT_CIRCLES && (desc->n_points != 1 || desc->dof < 2 || (desc->family & SCO_FAM_FLAG_EE_COST))) ||
-      (statefam && (desc->n_points != 1 || (desc->family & SCO_FAM_FLAG_EE_COST))) ||
-      (fam == SCO_FAM_STATE_QUADRATIC && desc->dof > OBJ_DMAX) ||
-      // blocks of `span` timesteps, equality rows and objective programs: the state families' extensions (r03)
-      desc->span < 0 || desc->span > 4 || desc->n_eq_rows < 0 || desc->n_eq_rows > desc->n_obstacles ||
-      (span > 1 && fam != SCO_FAM_STATE_PROGRAM) || (desc->n_eq_rows > 0 && !statefam) ||
-      (fam == SCO_FAM_STATE_PROGRAM && (span * desc->dof > SCO_STATE_MAX || span >= desc->horizon)) ||
-      ((desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) && (fam != SCO_FAM_STATE_PROGRAM || span != 1 || desc->dof > objmax)) ||
-      // an objective program per constraint block: span 2 .. 4, the block's state fits the per-thread eigenvalue sweep
-      ((desc->family & SCO_FAM_FLAG_OBJ_BLOCK) && (fam != SCO_FAM_STATE_PROGRAM || span < 2 || span * desc->dof > objmax ||
-                                                   (desc->family & (SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_EE_COST)))) ||
-      // SCO_FAM_FLAG_OBJ_WIDE: opt-in, the program family with exactly one of its two objective flags
-      (objwide && (fam != SCO_FAM_STATE_PROGRAM || (desc->family & SCO_FAM_FLAG_EE_COST) ||
-                   !(desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) == !(desc->family & SCO_FAM_FLAG_OBJ_BLOCK)))) {
-    sco_set_error("sco_sqp_create: bad descriptor"); return SCO_ERR_ARG;
-  }
+  const char *err = "";
+  if (int rc = sqp_check_desc(desc, n_rows, row_ptr, col_idx, row_is_eq, &err)) { sco_set_error(err); return rc; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     (void)hipGetLastError();
@@ -1300,12 +1002,7 @@ extern "C" int sco_sqp_create_rows(int device, const sco_trajopt_desc *desc, int
   SCO_ON_DEVICE(device);
   sco_sqp *h = new sco_sqp();
   h->device = device; h->desc = *desc;
-  if (n_rows > 0) {
-    h->gen_ptr.assign(row_ptr, row_ptr + n_rows + 1); h->gen_col.assign(col_idx, col_idx + row_ptr[n_rows]);
-    h->gen_iseq.resize(n_rows);
-    for (int r = 0; r < n_rows; r++) h->gen_iseq[r] = row_is_eq[r] ? 1 : 0;
-  }
-  const int rc = sqp_create_impl(h, device, desc);
+  const int rc = sqp_create_impl(h, device, sqp_layout_build(*desc, n_rows, row_ptr, col_idx, row_is_eq));
   if (rc) { sco_sqp_destroy(h); return rc; }       // frees whatever had been allocated
   *out = h;
   return SCO_OK;
@@ -1315,7 +1012,9 @@ extern "C" int sco_sqp_create(int device, const sco_trajopt_desc *desc, sco_sqp 
   return sco_sqp_create_rows(device, desc, 0, nullptr, nullptr, nullptr, out);
 }
 
-static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc) {
+// stream and allocations, the two QP handles fed from the layout (sqp_layout_build), and the uploads
+static int sqp_create_impl(sco_sqp *h, int device, const SqpLayout &L) {
+  const sco_trajopt_desc *desc = &h->desc;
   SCO_HIP(hipStreamCreate(&h->stream));
   SCO_HIP(hipHostMalloc((void **)&h->host_active, SQP_MAX_GROUPS * SQP_DEPTH * sizeof(int)));
   {
@@ -1324,138 +1023,28 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
     h->allocs.push_back(fb); h->fetch_buf = (double *)fb;
   }
   const int B = desc->batch, d = desc->dof, T = desc->horizon, K = desc->n_points, O = desc->n_obstacles;
-  const bool reach = (desc->family & 15) == SCO_FAM_ARM_REACH, vel = (desc->family & SCO_FAM_FLAG_VEL_LIMITS) != 0;
-  const bool jl = (desc->family & SCO_FAM_FLAG_JOINT_LIMITS) != 0;
-  const bool cost = (desc->family & (SCO_FAM_FLAG_EE_COST | SCO_FAM_FLAG_OBJ_PROGRAM | SCO_FAM_FLAG_OBJ_BLOCK)) != 0;
-  const bool oblk = (desc->family & SCO_FAM_FLAG_OBJ_BLOCK) != 0;
-  const bool acc = (desc->family & SCO_FAM_FLAG_ACC_COST) != 0;
-  const int NE = reach ? 2 : 0;                  // equality rows (end-effector x, y) on the last timestep
-  const int S = desc->span > 0 ? desc->span : 1, ds = S * d, NBt = T - S + 1, Req = desc->n_eq_rows;
-  const int m_pin = reach ? d : 2 * d, dT1 = d * (T - 1), m_vel = vel ? 2 * dT1 : 0;
-  const int m_jl = jl ? 2 * d * T : 0;
-  // a hinge row has one slack, an equality row two (prob.py:258, 285-286); block-major, hinge rows of a block first
-  // general affine rows (r04): column lists of the CSR pattern; entry k of the pattern = (row, column) in CSR order
-  const int m_gen = (int)h->gen_iseq.size(), nnz_gen = m_gen ? h->gen_ptr[m_gen] : 0;
-  std::vector<std::vector<std::pair<int, int>>> gen_of_col(d * T);       // (row, k), rows ascending
-  for (int r = 0; r < m_gen; r++)
-    for (int k = h->gen_ptr[r]; k < h->gen_ptr[r + 1]; k++) gen_of_col[h->gen_col[k]].push_back({r, k});
-  std::vector<int> gpos0(std::max(nnz_gen, 1), 0), gpos1(std::max(nnz_gen, 1), 0);
-  const int R = K * O, n_x = d * T, SB = R + Req, n_slack = NBt * SB + 2 * NE, n = n_x + n_slack, m_lin = m_pin + m_vel + m_jl + m_gen;
-  const int m_nl = NBt * R + NE, m = m_lin + m_nl + n;
-  // linear rows of column (t, j), ascending: pin, velocity rows "theta[t] - theta[t-1] <= vmax" (+1),
-  // "theta[t+1] - theta[t] <= vmax" (-1), then the two negated rows
-  auto linear_entries = [&](int t, int j, std::vector<int> &Ai, std::vector<double> &Av, std::vector<int> &gpos) {
-    if (t == 0) { Ai.push_back(j); Av.push_back(1.0); }
-    if (t == T - 1 && !reach) { Ai.push_back(d + j); Av.push_back(1.0); }
-    if (vel) {
-      if (t >= 1) { Ai.push_back(m_pin + (t - 1) * d + j); Av.push_back(1.0); }
-      if (t <= T - 2) { Ai.push_back(m_pin + t * d + j); Av.push_back(-1.0); }
-      if (t >= 1) { Ai.push_back(m_pin + dT1 + (t - 1) * d + j); Av.push_back(-1.0); }
-      if (t <= T - 2) { Ai.push_back(m_pin + dT1 + t * d + j); Av.push_back(1.0); }
-    }
-    if (jl) {
-      Ai.push_back(m_pin + m_vel + t * d + j); Av.push_back(1.0);
-      Ai.push_back(m_pin + m_vel + d * T + t * d + j); Av.push_back(-1.0);
-    }
-    for (const auto &rk : gen_of_col[t * d + j]) {        // values per problem (sco_sqp_load_linear_rows): 0 in the constants
-      gpos[rk.second] = (int)Ai.size();
-      Ai.push_back(m_pin + m_vel + m_jl + rk.first); Av.push_back(0.0);
-    }
-  };
-  std::vector<double> a0c, a1c;
-  // ---- projection QP pattern: P = diag, A = [linear rows ; I]
-  {
-    std::vector<int> Pp(n_x + 1), Pi(n_x), Ap(n_x + 1), Ai;
-    for (int i = 0; i < n_x; i++) { Pp[i] = i; Pi[i] = i; }
-    Pp[n_x] = n_x;
-    for (int col = 0; col < n_x; col++) {
-      Ap[col] = (int)Ai.size();
-      const int t = col / d, j = col % d;
-      linear_entries(t, j, Ai, a0c, gpos0);
-      Ai.push_back(m_lin + col); a0c.push_back(1.0);
-    }
-    Ap[n_x] = (int)Ai.size();
-    int rc = sco_qp_create_on_stream(device, B, n_x, m_lin + n_x, Pp.data(), Pi.data(), Ap.data(), Ai.data(), h->stream, &h->qp0);
-    if (rc) return rc;
-  }
-  // ---- penalty QP pattern (prob.py:251-278 rows, osqp_utils.py:185-189 bound rows)
-  std::vector<int> jpos(n_x), epos(d, 0), ppos(n_x, 0);
-  {
-    std::vector<int> Pp(n + 1), Pi, Ap(n + 1), Ai;
-    for (int col = 0; col < n; col++) {
-      Pp[col] = (int)Pi.size();
-      if (col < n_x && oblk) {
-        // block terms (SCO_FAM_FLAG_OBJ_BLOCK): a block's Hessian couples all its S timesteps, so column (t, j) holds the
-        // dense band of rows max(0, t - S + 1) d .. col -- with the acceleration term's (t - 2, j) in front when S = 2
-        const int t = col / d, r0 = std::max(0, t - S + 1) * d;
-        if (acc && S == 2 && t > 1) Pi.push_back(col - 2 * d);
-        ppos[col] = (int)Pi.size() - r0;           // entry (r, col) sits at ppos + r
-        for (int r = r0; r <= col; r++) Pi.push_back(r);
-      } else if (col < n_x) {
-        if (acc && col / d > 1) Pi.push_back(col - 2 * d);       // acceleration term (r04): second super-diagonal block
-        if (col / d > 0) Pi.push_back(col - d);
-        ppos[col] = (int)Pi.size();
-        // a non-quadratic objective term fills the upper triangle of its timestep's diagonal block
-        if (cost) for (int i = 0; i < col % d; i++) Pi.push_back(col - col % d + i);
-        else ppos[col] -= col % d;                 // entry (i, j) sits at ppos + i; only i == j exists
-        Pi.push_back(col);
-      }
-    }
-    Pp[n] = (int)Pi.size();
-    for (int col = 0; col < n; col++) {
-      Ap[col] = (int)Ai.size();
-      if (col < n_x) {
-        const int t = col / d, j = col % d;
-        linear_entries(t, j, Ai, a1c, gpos1);
-        jpos[col] = (int)Ai.size();
-        // Jacobian slots: the R rows of every block that covers timestep t (blocks t - S + 1 .. t), in block order
-        for (int blk = std::max(0, t - S + 1); blk <= std::min(t, NBt - 1); blk++)
-          for (int r = 0; r < R; r++) { Ai.push_back(m_lin + blk * R + r); a1c.push_back(0.0); }
-        if (t == T - 1 && reach) {
-          epos[j] = (int)Ai.size();
-          for (int r = 0; r < NE; r++) { Ai.push_back(m_lin + NBt * R + r); a1c.push_back(0.0); }
-        }
-        Ai.push_back(m_lin + m_nl + col); a1c.push_back(1.0);
-      } else {
-        // hinge slack i sits in hinge row i (-1); equality row r has p_r (slack T R + 2 r, -1) and n_r (+1)
-        // (prob.py:265-275, 303-312); then the slack's bound row
-        // slack columns block-major: per block its R - Req hinge slacks, then (p, n) of each of its Req equality rows;
-        // behind the blocks (p, n) of the reach rows
-        const int sidx = col - n_x;
-        int row; double sgn = -1.0;
-        if (sidx < NBt * SB) {
-          const int blk = sidx / SB, k = sidx % SB, nh = R - Req;
-          if (k < nh) row = blk * R + k;
-          else { row = blk * R + nh + (k - nh) / 2; if ((k - nh) & 1) sgn = 1.0; }
-        } else {
-          const int ke = sidx - NBt * SB;
-          row = NBt * R + ke / 2; if (ke & 1) sgn = 1.0;
-        }
-        Ai.push_back(m_lin + row); a1c.push_back(sgn);
-        Ai.push_back(m_lin + m_nl + col); a1c.push_back(1.0);
-      }
-    }
-    Ap[n] = (int)Ai.size();
-    int rc = sco_qp_create_on_stream(device, B, n, m, Pp.data(), Pi.data(), Ap.data(), Ai.data(), h->stream, &h->qp1);
-    if (rc) return rc;
-  }
+  const int n_x = L.n_x, m_nl = L.m_nl, ds = L.ds, NBt = L.NBt;
+  const bool cost = L.cost != OBJ_NONE, oblk = L.cost == OBJ_BLOCK;
+  int rc = sco_qp_create_on_stream(device, B, n_x, L.m_lin + n_x, L.qp0.Pp.data(), L.qp0.Pi.data(), L.qp0.Ap.data(), L.qp0.Ai.data(),
+                                   h->stream, &h->qp0);
+  if (rc) return rc;
+  rc = sco_qp_create_on_stream(device, B, L.n, L.m, L.qp1.Pp.data(), L.qp1.Pi.data(), L.qp1.Ap.data(), L.qp1.Ai.data(), h->stream, &h->qp1);
+  if (rc) return rc;
   SqpDev &s = h->d;
-  s.batch = B; s.d = d; s.T = T; s.K = K; s.O = O; s.R = R; s.n_x = n_x; s.n_slack = n_slack; s.n = n;
-  s.m_lin = m_lin; s.m_nl = m_nl; s.m = m; s.prox_count = desc->prox_count > 0 ? desc->prox_count : 1;
+  s.batch = B; s.d = d; s.T = T; s.K = K; s.O = O; s.R = L.R; s.n_x = n_x; s.n_slack = L.n_slack; s.n = L.n;
+  s.m_lin = L.m_lin; s.m_nl = m_nl; s.m = L.m; s.prox_count = desc->prox_count > 0 ? desc->prox_count : 1;
   s.analytic_jac = desc->analytic_jac; s.trace_cap = 64;
-  s.point = (desc->family & 15) == SCO_FAM_POINT_CIRCLES ? 1 : (desc->family & 15) == SCO_FAM_STATE_QUADRATIC ? 2 :
-            (desc->family & 15) == SCO_FAM_STATE_PROGRAM ? 3 : 0;
-  s.NE = NE; s.NB = NBt + (reach ? 1 : 0); s.RM = std::max(R, NE) + (cost ? 1 : 0);     // + the objective term's value
-  s.S = S; s.ds = ds; s.NBt = NBt; s.Req = Req;
-  s.m_gen = m_gen; s.nnz_gen = nnz_gen;
-  s.acc = acc ? 1 : 0;
-  s.m_pin = m_pin; s.m_vel = m_vel; s.m_jl = m_jl; s.cost = oblk ? 3 : (desc->family & SCO_FAM_FLAG_OBJ_PROGRAM) ? 2 : cost ? 1 : 0;
-  int rc = 0;
+  s.point = L.point;
+  s.NE = L.NE; s.NB = L.NB; s.RM = L.RM;
+  s.S = L.S; s.ds = ds; s.NBt = NBt; s.Req = L.Req;
+  s.m_gen = L.m_gen; s.nnz_gen = L.nnz_gen;
+  s.acc = L.acc;
+  s.m_pin = L.m_pin; s.m_vel = L.m_vel; s.m_jl = L.m_jl; s.cost = L.cost;
 #define AL(f, cnt) if ((rc = sq_alloc(h, (cnt), &s.f))) return rc;
   AL(x0, (size_t)B * n_x) AL(start, (size_t)B * d) AL(goal, (size_t)B * d) AL(link_len, (size_t)B * d)
   AL(obstacles, (size_t)B * O * 3) AL(target, (size_t)B * 2) AL(vmax, (size_t)B) AL(jlo, (size_t)B * d) AL(jhi, (size_t)B * d)
   {
-    const bool quadf = (desc->family & 15) == SCO_FAM_STATE_QUADRATIC;
+    const bool quadf = L.point == ROWS_QUADRATIC;
     AL(qQ, quadf ? (size_t)B * O * ds * ds : 1) AL(qa, quadf ? (size_t)B * O * ds : 1) AL(qc, quadf ? (size_t)B * O : 1)
   }
   AL(x, (size_t)B * n_x) AL(x_saved, (size_t)B * n_x) AL(gsave, (size_t)B * m_nl) AL(J, (size_t)B * m_nl * ds)
@@ -1486,37 +1075,21 @@ static int sqp_create_impl(sco_sqp *h, int device, const sco_trajopt_desc *desc)
     }
     AL(oA, cost ? (size_t)B * NO * dO : 1) AL(ob, cost ? (size_t)B * NO : 1)
   }
+  AL(mvec, (size_t)B * 32) AL(nonconv, (size_t)B) AL(stalled, (size_t)B)
 #undef AL
-  { int *p; if ((rc = sq_alloc(h, (size_t)n_x, &p))) return rc; s.ppos = p;
-    SCO_HIP(hipMemcpy(p, ppos.data(), n_x * sizeof(int), hipMemcpyHostToDevice)); }
   { int *p; if ((rc = sq_alloc(h, (size_t)K, &p))) return rc; s.point_link = p; }
   { double *p; if ((rc = sq_alloc(h, (size_t)K, &p))) return rc; s.point_frac = p; }
-  { int *p; if ((rc = sq_alloc(h, (size_t)n_x, &p))) return rc; s.jpos = p;
-    SCO_HIP(hipMemcpy(p, jpos.data(), n_x * sizeof(int), hipMemcpyHostToDevice)); }
-  { double *p; if ((rc = sq_alloc(h, a0c.size(), &p))) return rc; s.a0c = p;
-    SCO_HIP(hipMemcpy(p, a0c.data(), a0c.size() * sizeof(double), hipMemcpyHostToDevice)); }
-  { double *p; if ((rc = sq_alloc(h, a1c.size(), &p))) return rc; s.a1c = p;
-    SCO_HIP(hipMemcpy(p, a1c.data(), a1c.size() * sizeof(double), hipMemcpyHostToDevice)); }
   { unsigned int *p; if ((rc = sq_alloc(h, (size_t)s.NB, &p))) return rc; s.gmask = p; }
   { unsigned int *p; if ((rc = sq_alloc(h, (size_t)32, &p))) return rc; s.goverlap = p; }
-  if ((rc = sq_alloc(h, (size_t)B * 32, &s.mvec))) return rc;
-  if ((rc = sq_alloc(h, (size_t)B, &s.nonconv))) return rc;
-  if ((rc = sq_alloc(h, (size_t)B, &s.stalled))) return rc;
   s.G = 0;
-  { int *p; if ((rc = sq_alloc(h, (size_t)d, &p))) return rc; s.epos = p;
-    SCO_HIP(hipMemcpy(p, epos.data(), d * sizeof(int), hipMemcpyHostToDevice)); }
-  s.bpos = nullptr;
+  if ((rc = sq_upload(h, L.ppos, &s.ppos)) || (rc = sq_upload(h, L.jpos, &s.jpos)) || (rc = sq_upload(h, L.epos, &s.epos)) ||
+      (rc = sq_upload(h, L.a0c, &s.a0c)) || (rc = sq_upload(h, L.a1c, &s.a1c))) return rc;
   s.gen_eq = s.gpos0 = s.gpos1 = nullptr; s.gen_rhs = s.gen_val = nullptr;
-  if (m_gen) {
-    int *p; double *q;
-    if ((rc = sq_alloc(h, (size_t)m_gen, &p))) return rc;
-    SCO_HIP(hipMemcpy(p, h->gen_iseq.data(), m_gen * sizeof(int), hipMemcpyHostToDevice)); s.gen_eq = p;
-    if ((rc = sq_alloc(h, (size_t)nnz_gen, &p))) return rc;
-    SCO_HIP(hipMemcpy(p, gpos0.data(), nnz_gen * sizeof(int), hipMemcpyHostToDevice)); s.gpos0 = p;
-    if ((rc = sq_alloc(h, (size_t)nnz_gen, &p))) return rc;
-    SCO_HIP(hipMemcpy(p, gpos1.data(), nnz_gen * sizeof(int), hipMemcpyHostToDevice)); s.gpos1 = p;
-    if ((rc = sq_alloc(h, (size_t)B * m_gen, &q))) return rc; s.gen_rhs = q;
-    if ((rc = sq_alloc(h, (size_t)B * nnz_gen, &q))) return rc; s.gen_val = q;
+  if (L.m_gen) {
+    double *q;
+    if ((rc = sq_upload(h, L.gen_eq, &s.gen_eq)) || (rc = sq_upload(h, L.gpos0, &s.gpos0)) || (rc = sq_upload(h, L.gpos1, &s.gpos1))) return rc;
+    if ((rc = sq_alloc(h, (size_t)B * L.m_gen, &q))) return rc; s.gen_rhs = q;
+    if ((rc = sq_alloc(h, (size_t)B * L.nnz_gen, &q))) return rc; s.gen_val = q;
   }
   return SCO_OK;
 }
@@ -1641,34 +1214,12 @@ static int load_program_impl(sco_sqp *h, int n_words, const int *words, const in
   }
   if ((h->desc.family & 15) != SCO_FAM_STATE_PROGRAM) { sco_set_error("sco_sqp_load_program: family has no row programs"); return SCO_ERR_ARG; }
   if (!h->loaded) { sco_set_error("sco_sqp_load_program: call sco_sqp_load first"); return SCO_ERR_STATE; }
-  // the rows of a block, then (SCO_FAM_FLAG_OBJ_PROGRAM) the objective term of a timestep or (SCO_FAM_FLAG_OBJ_BLOCK) of a block
-  const int R = h->d.O - h->d.R1 + (h->d.cost >= 2 ? 1 : 0), ds = h->d.ds;       // (r04: R1 leading rows of a block are circle rows)
-  if (n_words <= 0 || n_consts < 0 || n_params < 0) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
-  // the whole of row_ptr is checked BEFORE any word is read through it: 0 = first entry, strictly increasing, last = n_words
-  if (row_ptr[0] != 0) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
-  for (int r = 0; r < R; r++)
-    if (row_ptr[r + 1] <= row_ptr[r] || row_ptr[r + 1] > n_words) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
-  if (row_ptr[R] != n_words) { sco_set_error("sco_sqp_load_program: bad program layout"); return SCO_ERR_ARG; }
-  // every row's program is run on the host once, symbolically: stack depth and operand indices
-  for (int r = 0; r < R; r++) {
-    if (words[2 * (row_ptr[r + 1] - 1)] != SCO_OP_END) {
-      sco_set_error("sco_sqp_load_program: a row's program must end with SCO_OP_END"); return SCO_ERR_ARG;
-    }
-    const int nx = (r < h->d.O - h->d.R1 || h->d.cost == 3) ? ds : h->d.d;      // the objective term sees one timestep (a block's: ds)
-    int sp = 0;
-    for (int w = row_ptr[r]; w < row_ptr[r + 1] - 1; w++) {
-      const int op = words[2 * w], arg = words[2 * w + 1];
-      bool ok = true;
-      if (op == SCO_OP_X) { ok = arg >= 0 && arg < nx; sp++; }
-      else if (op == SCO_OP_P) { ok = arg >= 0 && arg < n_params; sp++; }
-      else if (op == SCO_OP_C) { ok = arg >= 0 && arg < n_consts; sp++; }
-      else if (op >= SCO_OP_ADD && op <= SCO_OP_DIV) { ok = sp >= 2; sp--; }
-      else if (op >= SCO_OP_NEG && op <= SCO_OP_SQUARE) ok = sp >= 1;
-      else ok = false;
-      if (!ok || sp > SCO_PROGRAM_STACK) { sco_set_error("sco_sqp_load_program: malformed program (operand index, stack depth or opcode)"); return SCO_ERR_ARG; }
-    }
-    if (sp != 1) { sco_set_error("sco_sqp_load_program: a row's program must leave exactly one value"); return SCO_ERR_ARG; }
+  // the rows of a block (behind its R1 circle rows), then the objective term's program: layout, stack depth, operands
+  const char *err = "";
+  if (int rc = sqp_check_program(h->d.O - h->d.R1, h->d.cost, h->d.ds, h->d.d, n_words, words, row_ptr, n_consts, n_params, &err)) {
+    sco_set_error(err); return rc;
   }
+  const int R = h->d.O - h->d.R1 + (obj_is_program(h->d.cost) ? 1 : 0);
   SCO_ON_DEVICE(h->device);
   SqpDev &s = h->d;
   // the four buffers belong to the handle: a reload of the same sizes (new parameters per solve) reuses them, another
@@ -2308,6 +1859,42 @@ extern "C" int sco_sqp_last_rounds(const sco_sqp *h, int *rounds) {
   if (!h || !rounds) return SCO_ERR_ARG;
   *rounds = h->rounds;
   return SCO_OK;
+}
+
+// The layout and the program check on plain numbers (include/sco_hip.h): no device is touched
+extern "C" int sco_debug_sqp_layout(const sco_trajopt_desc *desc, int n_rows, const int *row_ptr, const int *col_idx, const int *row_is_eq,
+                                    int dims[22], int sizes[15], int *ints, double *vals) {
+  if (!dims || !sizes) { sco_set_error("sco_debug_sqp_layout: null pointer"); return SCO_ERR_ARG; }
+  const char *err = "";
+  if (int rc = sqp_check_desc(desc, n_rows, row_ptr, col_idx, row_is_eq, &err)) { sco_set_error(err); return rc; }
+  const SqpLayout L = sqp_layout_build(*desc, n_rows, row_ptr, col_idx, row_is_eq);
+  const int dm[22] = {L.NE, L.S, L.ds, L.NBt, L.Req, L.m_pin, L.m_vel, L.m_jl, L.m_gen, L.nnz_gen, L.R, L.n_x, L.n_slack, L.n,
+                      L.m_lin, L.m_nl, L.m, L.NB, L.RM, L.point, L.cost, L.acc};
+  memcpy(dims, dm, sizeof dm);
+  const std::vector<int> *iv[13] = {&L.qp0.Pp, &L.qp0.Pi, &L.qp0.Ap, &L.qp0.Ai, &L.qp1.Pp, &L.qp1.Pi, &L.qp1.Ap, &L.qp1.Ai,
+                                    &L.jpos, &L.epos, &L.ppos, &L.gpos0, &L.gpos1};
+  const std::vector<double> *dv[2] = {&L.a0c, &L.a1c};
+  for (int k = 0; k < 13; k++) {
+    sizes[k] = (int)iv[k]->size();
+    if (ints) ints = std::copy(iv[k]->begin(), iv[k]->end(), ints);
+  }
+  for (int k = 0; k < 2; k++) {
+    sizes[13 + k] = (int)dv[k]->size();
+    if (vals) vals = std::copy(dv[k]->begin(), dv[k]->end(), vals);
+  }
+  return SCO_OK;
+}
+extern "C" int sco_debug_sqp_check_program(const sco_trajopt_desc *desc, int n_circle_rows, int n_words, const int *words,
+                                           const int *row_ptr, int n_consts, int n_params) {
+  const char *err = "";
+  if (int rc = sqp_check_desc(desc, 0, nullptr, nullptr, nullptr, &err)) { sco_set_error(err); return rc; }
+  if (!words || !row_ptr) { sco_set_error("sco_sqp_load_program: null pointer"); return SCO_ERR_ARG; }
+  if ((desc->family & 15) != SCO_FAM_STATE_PROGRAM) { sco_set_error("sco_sqp_load_program: family has no row programs"); return SCO_ERR_ARG; }
+  const SqpLayout L = sqp_layout_build(*desc, 0, nullptr, nullptr, nullptr);
+  if (n_circle_rows < 0 || n_circle_rows >= desc->n_obstacles) { sco_set_error("sco_debug_sqp_check_program: bad circle-row count"); return SCO_ERR_ARG; }
+  const int rc = sqp_check_program(desc->n_obstacles - n_circle_rows, L.cost, L.ds, desc->dof, n_words, words, row_ptr, n_consts, n_params, &err);
+  if (rc) sco_set_error(err);
+  return rc;
 }
 
 extern "C" int sco_debug_sqp_wv_rounds(const sco_sqp *h) { return h ? h->wv_rounds : -1; }
