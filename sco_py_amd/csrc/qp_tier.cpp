@@ -11,6 +11,10 @@ QpCreateEnv qp_create_env() {
   e.factor_cholesky = on("SCO_QP_FACTOR_CHOLESKY"); e.no_elim = on("SCO_QP_NO_ELIM");
   e.force_big = on("SCO_QP_FORCE_BIG"); e.no_bt = on("SCO_QP_NO_BT");
   e.no_rl = on("SCO_QP_NO_RL"); e.no_wv = on("SCO_QP_NO_WV"); e.no_reg = on("SCO_QP_NO_REG"); e.no_fast = on("SCO_QP_NO_FAST");
+  e.no_mfma = on("SCO_QP_NO_MFMA");
+  e.rl_closed = on("SCO_QP_RL_ALIGNED") || on("SCO_QP_RL_CLOSED"); e.rl_lay8 = on("SCO_QP_RL_LAY8");
+  { const char *v = getenv("SCO_QP_RL_SPLIT"); e.rl_split_off = v && v[0] == '0'; }
+  e.debug_plan = getenv("SCO_DEBUG_PLAN") != nullptr;
   return e;
 }
 

@@ -3,20 +3,31 @@
 // What a launch on a handle does -- which checks it fails, the slice, the tier, which problems get the dense inverse,
 // the factor kernel, the sequence of ADMM launches -- is decided here from plain numbers, so that it can be read, and
 // tested, without a GPU (tests/test_qp_launch_plan.py, through sco_debug_qp_launch_plan).  sco_qp_launch_sliced issues
-// what the plan says and decides nothing again.  The environment of the QP layer is read here and nowhere else.
+// what the plan says and decides nothing again.
+//
+// What sco_qp_create decides from the environment is read here and nowhere else (qp_create_env): the tier choice and
+// every tier planner take a QpCreateEnv and call getenv nowhere.  Three launch-time variables are read elsewhere, on
+// purpose, at every launch: SCO_WV_MIN_PER_CU below (sco_wv_min_live), SCO_QP_BT_TRIPLE in big_launch (sco_qp_big.hip) and
+// SCO_WV_ABLATE in wv_fill_args (sco_admm_wv.hip; only a -DWV_ABLATE build acts on it).
 #pragma once
 #include "../../include/sco_hip.h"
 
 #define SCO_FACTOR_BLOCK 1024   // threads of the factor kernels (qp_sweep_kernel, qp_factor_kernel)
 
 // The create-time switches, read once per sco_qp_create (qp_create_env).  Each is on only when the variable's first
-// character is '1'.
+// character is '1', but for the last two.
 struct QpCreateEnv {
   bool factor_cholesky = false;  // SCO_QP_FACTOR_CHOLESKY: W by Cholesky + triangular inverse (cross-check)
   bool no_elim = false;          // SCO_QP_NO_ELIM: no variable is eliminated (dense core of order n)
   bool force_big = false;        // SCO_QP_FORCE_BIG: the global-memory tier whatever the working set
   bool no_bt = false;            // SCO_QP_NO_BT: not its structured form
   bool no_rl = false, no_wv = false, no_reg = false, no_fast = false;   // SCO_QP_NO_RL / _WV / _REG / _FAST
+  // what the tier planners read
+  bool no_mfma = false;          // SCO_QP_NO_MFMA: structured global-memory form without the matrix cores (bt_plan_build)
+  bool rl_closed = false;        // SCO_QP_RL_ALIGNED or SCO_QP_RL_CLOSED: the aligned closed assignment (rl_plan_build)
+  bool rl_lay8 = false;          // SCO_QP_RL_LAY8: 8 column groups of the W tile with the open assignment
+  bool rl_split_off = false;     // SCO_QP_RL_SPLIT: on only at '0' -- a column's pairs all on the owner lane
+  bool debug_plan = false;       // SCO_DEBUG_PLAN: on when set -- the closed assignment prints its components to stderr
 };
 QpCreateEnv qp_create_env();
 

@@ -21,66 +21,11 @@
 //     the core right-hand side and solution) go through LDS;
 //   * HBM is read once (problem + W) and written once (answer).
 #include "sco_admm_check.h"
+#include "layout_fast.h"    // workgroup and W tiling: shared with fast_plan_build (reg_fast_plan.cpp)
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-
-#define FT 512            // threads per workgroup
-#define FW (FT / 64)      // wavefronts per workgroup
-#define GJ 16             // column groups of the W tiling
-#define GI (FT / GJ)      // row groups (32)
-
-// --------------------------------------------------------------------------
-// host: sliced-ELL construction
-// --------------------------------------------------------------------------
-void build_sell(int nitems, const std::vector<int> &ptr, const std::vector<int> &idx,
-                       const std::vector<int> &src, SellHost &out) {
-  out.nitems = nitems;
-  const int ns = (nitems + 63) / 64;
-  out.base.assign(ns + 1, 0); out.width.assign(std::max(ns, 1), 0);
-  for (int s = 0; s < ns; s++) {
-    int w = 0;
-    for (int it = s * 64; it < std::min(nitems, s * 64 + 64); it++) w = std::max(w, ptr[it + 1] - ptr[it]);
-    out.width[s] = w; out.base[s + 1] = out.base[s] + 64 * w;
-  }
-  out.total = out.base[ns];
-  out.idx.assign(std::max(out.total, 1), 0); out.src.assign(std::max(out.total, 1), -1);
-  for (int it = 0; it < nitems; it++) {
-    const int s = it / 64, l = it % 64;
-    for (int k = 0; k < ptr[it + 1] - ptr[it]; k++) {
-      const int p = out.base[s] + 64 * k + l;
-      out.idx[p] = (unsigned short)idx[ptr[it] + k];
-      out.src[p] = src[ptr[it] + k];
-    }
-  }
-}
-
-bool fast_plan_build(const QpPlan &pl, FastHost &fh) {
-  if (pl.n > FT || pl.m > 3 * FT || pl.nnzA >= 65536 || pl.n_c > 32 * 5) return false;
-  std::vector<int> ident(std::max(pl.nnzA, pl.ncpl) + 1);
-  for (size_t i = 0; i < ident.size(); i++) ident[i] = (int)i;
-  build_sell(pl.n, pl.Ap, pl.Ai, ident, fh.Ac);                       // A by column: idx = row, src = CSC position
-  build_sell(pl.m, pl.Rp, pl.Rj, pl.Rpos, fh.Ar);                      // A by row:    idx = column
-  {
-    std::vector<int> eidx(pl.ncpl), srck(pl.ncpl);
-    for (int t = 0; t < pl.ncpl; t++) { eidx[t] = pl.pair_elim[pl.a_pair[t]]; srck[t] = pl.a_pair[t]; }
-    build_sell(pl.n_c, pl.a_ptr, eidx, srck, fh.Ca);                   // K_CE by core: idx = eliminated index
-  }
-  build_sell(pl.n_e, pl.e_ptr, pl.pair_core, ident, fh.Ce);            // K_CE by eliminated: idx = core index
-  fh.TR = std::max(1, (pl.n_c + GI - 1) / GI);
-  fh.TC = 2 * fh.TR;
-  if (fh.TR == 5 && pl.n_c <= GJ * 9) fh.TC = 9;        // 140-order core: 5 x 9 tile
-  auto maxw = [](const SellHost &h) { int w = 0; for (int x : h.width) w = std::max(w, x); return w; };
-  fh.capped = maxw(fh.Ac) <= 12 && maxw(fh.Ar) <= 8 && maxw(fh.Ca) <= 12 && maxw(fh.Ce) <= 8;
-  const int ps = GI * fh.TR + 1;
-  const size_t scratch = std::max<size_t>((size_t)GJ * ps, 2 * (size_t)pl.n + 2 * (size_t)pl.m);
-  fh.lds_doubles = (size_t)fh.Ac.total + fh.Ar.total + fh.Ca.total + fh.Ce.total +   // values
-                   pl.n + pl.m + pl.n_e + (size_t)GJ * fh.TC + (size_t)GI * fh.TR +  // xt, t, ge, r, xc
-                   scratch + FW * 8;
-  fh.lds_bytes = fh.lds_doubles * 8 + 2 * ((size_t)fh.Ac.total + fh.Ar.total + fh.Ca.total + fh.Ce.total + 8 + 64 * 12);
-  return fh.lds_bytes <= 160 * 1024;
-}
 
 // --------------------------------------------------------------------------
 // device

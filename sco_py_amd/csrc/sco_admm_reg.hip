@@ -24,113 +24,11 @@
 //   * kernel arguments are a slim struct (no SGPR spills in the loop);
 //   * r03: the solve parks and resumes like the other on-chip kernels (time slicing, adaptive rho).
 #include "sco_admm_check.h"
+#include "layout_reg.h"     // workgroup, W tiling, caps and static LDS: shared with reg_plan_build (reg_fast_plan.cpp)
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-
-#define RT 512
-#define RWV (RT / 64)
-#define RGJ 16
-#define RGI (RT / RGJ)
-#define CAP_N 512
-#define CAP_M 1024
-#define CAP_NC 160
-// static LDS of qp_admm_reg_kernel: its seven __shared__ arrays (s_xt, s_tv, s_ge, s_xc, s_rv, s_scr, s_red)
-#define REG_STATIC_LDS (8 * (4 * CAP_N + 3 * CAP_M + 2 * CAP_NC + RWV * 8))
-static_assert(REG_STATIC_LDS == 44032, "static LDS of qp_admm_reg_kernel");
-size_t reg_static_lds() { return REG_STATIC_LDS; }
-
-// --------------------------------------------------------------------------
-// host: per-thread programs
-// --------------------------------------------------------------------------
-void build_sell(int nitems, const std::vector<int> &ptr, const std::vector<int> &idx,
-                const std::vector<int> &src, SellHost &out);   // sco_admm_fast.hip
-
-bool reg_plan_build(const QpPlan &pl, int CW, int RW, int PX, RegHost &rh) {
-  // one spare element per gathered vector serves as the always-zero target of padded slots
-  if (pl.n >= CAP_N || pl.m >= CAP_M || pl.n_c >= CAP_NC || pl.n_e >= CAP_N || pl.nnzA >= 65536) return false;
-  rh.CW = CW; rh.RW = RW; rh.PX = PX;
-  {
-    std::vector<int> ident(std::max(pl.nnzA, pl.ncpl) + 1);
-    for (size_t i = 0; i < ident.size(); i++) ident[i] = (int)i;
-    build_sell(pl.n, pl.Ap, pl.Ai, ident, rh.Ac);
-    build_sell(pl.m, pl.Rp, pl.Rj, pl.Rpos, rh.Ar);
-    std::vector<int> eidx(pl.ncpl), srck(pl.ncpl);
-    for (int t = 0; t < pl.ncpl; t++) { eidx[t] = pl.pair_elim[pl.a_pair[t]]; srck[t] = pl.a_pair[t]; }
-    build_sell(pl.n_c, pl.a_ptr, eidx, srck, rh.Ca);
-    build_sell(pl.n_e, pl.e_ptr, pl.pair_core, ident, rh.Ce);
-    // room for the unrolled reads that run past the last slice
-    rh.lds_bytes = 8 * ((size_t)rh.Ac.total + rh.Ar.total + rh.Ca.total + rh.Ce.total + 64 * 16);
-    if (rh.lds_bytes + REG_STATIC_LDS > 160 * 1024) return false;
-  }
-  rh.TR = std::max(1, (pl.n_c + RGI - 1) / RGI);
-  rh.TC = 2 * rh.TR;
-  if (rh.TR == 5 && pl.n_c <= RGJ * 9) rh.TC = 9;
-  const int slots = CW + 2 * RW + PX;
-  rh.off.assign((size_t)slots * RT, 0);
-  rh.role.assign((size_t)8 * RT, -1);     // [0] core owned, [1] core variable, [2] elim index,
-                                          // [3] col base, [4] row0 base, [5] row1 base, [6] pair base (LDS element index)
-  // padded slots gather the spare zero element of their vector
-  for (int t = 0; t < RT; t++) {
-    for (int k = 0; k < CW; k++) rh.off[(size_t)k * RT + t] = (unsigned short)(8 * pl.m);
-    for (int k = 0; k < 2 * RW; k++) rh.off[(size_t)(CW + k) * RT + t] = (unsigned short)(8 * pl.n);
-    for (int k = 0; k < PX; k++) rh.off[(size_t)(CW + 2 * RW + k) * RT + t] = (unsigned short)(8 * pl.n_c);
-    rh.role[(size_t)3 * RT + t] = 0; rh.role[(size_t)4 * RT + t] = 0; rh.role[(size_t)5 * RT + t] = 0;
-    rh.role[(size_t)6 * RT + t] = 0;
-  }
-  // columns: thread j
-  for (int j = 0; j < pl.n; j++) {
-    const int w = pl.Ap[j + 1] - pl.Ap[j];
-    if (w > CW) return false;
-    for (int k = 0; k < w; k++)
-      rh.off[(size_t)k * RT + j] = (unsigned short)(8 * pl.Ai[pl.Ap[j] + k]);      // byte offset into t / w*y
-    rh.role[(size_t)3 * RT + j] = rh.Ac.base[j / 64] + (j % 64);
-  }
-  // rows: thread i % RT, slot i / RT
-  for (int i = 0; i < pl.m; i++) {
-    const int w = pl.Rp[i + 1] - pl.Rp[i];
-    if (w > RW) return false;
-    const int t = i % RT, q = i / RT;
-    for (int k = 0; k < w; k++)
-      rh.off[(size_t)(CW + q * RW + k) * RT + t] = (unsigned short)(8 * pl.Rj[pl.Rp[i] + k]);   // into x~ / x
-    rh.role[(size_t)(4 + q) * RT + t] = rh.Ar.base[i / 64] + (i % 64);
-  }
-  // eliminated variables: owner = the thread of their column
-  std::vector<char> elim_owner(RT, 0);
-  for (int e = 0; e < pl.n_e; e++) {
-    const int t = pl.elim_var[e];
-    const int w = pl.e_ptr[e + 1] - pl.e_ptr[e];
-    if (w > PX) return false;
-    elim_owner[t] = 1;
-    rh.role[(size_t)2 * RT + t] = e;
-    for (int k = 0; k < w; k++)
-      rh.off[(size_t)(CW + 2 * RW + k) * RT + t] = (unsigned short)(8 * pl.pair_core[pl.e_ptr[e] + k]);   // into x_C
-    rh.role[(size_t)6 * RT + t] = rh.Ac.total + rh.Ar.total + rh.Ca.total + rh.Ce.base[e / 64] + (e % 64);
-  }
-  // core variables: prefer threads without a column, never an eliminated-variable owner
-  {
-    std::vector<int> cand;
-    for (int t = RT - 1; t >= pl.n; t--) cand.push_back(t);
-    for (int t = 0; t < pl.n; t++) if (!elim_owner[t]) cand.push_back(t);
-    if ((int)cand.size() < pl.n_c) return false;
-    for (int c = 0; c < pl.n_c; c++) {
-      const int t = cand[c];
-      const int w = pl.a_ptr[c + 1] - pl.a_ptr[c];
-      if (w > PX) return false;
-      rh.role[t] = c;
-      rh.role[(size_t)RT + t] = pl.core_var[c];
-      for (int k = 0; k < PX; k++)       // padded slots of a core owner gather the zero element of g_E
-        rh.off[(size_t)(CW + 2 * RW + k) * RT + t] = (unsigned short)(8 * pl.n_e);
-      for (int k = 0; k < w; k++) {
-        const int pair = pl.a_pair[pl.a_ptr[c] + k];
-        rh.off[(size_t)(CW + 2 * RW + k) * RT + t] = (unsigned short)(8 * pl.pair_elim[pair]);   // into g_E
-      }
-      rh.role[(size_t)6 * RT + t] = rh.Ac.total + rh.Ar.total + rh.Ca.base[c / 64] + (c % 64);
-    }
-  }
-  return true;
-}
 
 // --------------------------------------------------------------------------
 // device
@@ -506,18 +404,6 @@ static int reg_launch_one(const RegArgs &ra, int batch, size_t lds, hipStream_t 
   hipLaunchKernelGGL((qp_admm_reg_kernel<TR, TC, CW, RW, PX>), dim3(batch), dim3(RT), lds, st, ra);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
-}
-
-// cap sets instantiated: A = (12, 8, 10) [7-DOF x 20 penalty QP], B = (12, 8, 12) generic small
-int reg_caps_for(const QpPlan &pl, int *CW, int *RW, int *PX) {
-  int cw = 0, rw = 0, px = 0;
-  for (int j = 0; j < pl.n; j++) cw = std::max(cw, pl.Ap[j + 1] - pl.Ap[j]);
-  for (int i = 0; i < pl.m; i++) rw = std::max(rw, pl.Rp[i + 1] - pl.Rp[i]);
-  for (int c = 0; c < pl.n_c; c++) px = std::max(px, pl.a_ptr[c + 1] - pl.a_ptr[c]);
-  for (int e = 0; e < pl.n_e; e++) px = std::max(px, pl.e_ptr[e + 1] - pl.e_ptr[e]);
-  if (cw > 12 || rw > 8 || px > 12) return 0;
-  *CW = 12; *RW = 8; *PX = px <= 10 ? 10 : 12;
-  return 1;
 }
 
 int reg_launch(const AdmmArgs &a, const RegHost &rh, const RegDev &rd, hipStream_t st) {

@@ -42,13 +42,12 @@
 #include <type_traits>
 
 #include "sco_admm_check.h"
+#include "layout_wv.h"      // lane tables, block positions, LDS and constant slots: shared with wv_plan_build (wv_plan.cpp)
 
-#define WV_T 64
+// timing switches of diagnostic builds (scripts/build_ablate.py wv:...); none of them changes the layout
 #ifndef WV_PD
 #define WV_PD 3       // block steps between the LDS reads of a sweep step and its arithmetic
 #endif
-#define WV_MAXNS 4
-#define WV_MAXNV 4
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 // (a VALU write of the broadcast operand needs two wait states before a DPP instruction reads it: the first of a chain
@@ -56,9 +55,6 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // a volatile statement is a scheduling barrier, and the loads of the next block step have to move above this one's chain)
 #ifndef WV_KEEP
 #define WV_KEEP 8        // blocks of G per chain the forward sweep keeps in registers for the backward sweep
-#endif
-#ifndef WV_JREG
-#define WV_JREG 1
 #endif
 #ifndef WV_VARIANT
 #define WV_VARIANT 0          // timing variants (scripts/build_ablate.py wv:WV_VARIANT=1): 1 = plain v_fmac_f64 instead of the DPP broadcasts (results wrong)
@@ -73,301 +69,8 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
 #endif
 
-__host__ __device__ __forceinline__ size_t wv_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }   // packed lower, j <= i
-
-// LDS layouts chosen against bank conflicts (r04 PMC: 42 % of the LDS cycles of the first version were conflicts, the LDS
-// pipe of a CU with four of these wavefronts was busy 68 % of the time).  A 64-byte row per lane at a 64-byte lane stride
-// puts lanes i and i + 4 on the same banks for every 16-byte piece; instead the four pieces of a vector are stored
-// PIECE-MAJOR, 16 bytes per block (or per lane slot) inside a piece:
-//   block vectors (r, x~, x, extra)  index(pos, k) = (k >> 1) * 2 NPOS + 2 pos + (k & 1)
-//   partial column sums              index(j, slot) = j * 2 NSLOT + 2 slot              (slot = pos * lpb + part)
-//   rows of G, block pos             index(row i, col c) = 64 pos + 16 ((c >> 1) + shift & 3) + 2 i + (c & 1), shift = 1 for
-//                                    the blocks of chain B (both chains read their piece j in the same instruction)
-__host__ __device__ inline int wv_vidx(int npos, int pos, int k) { return (k >> 1) * 2 * npos + 2 * pos + (k & 1); }
-__host__ __device__ inline int wv_gidx(int nstep, int pos, int i, int c) { return 64 * pos + 16 * (((c >> 1) + (pos > nstep ? 1 : 0)) & 3) + 2 * i + (c & 1); }
-
-// The G-resident sweep (WV_GRES, qp_admm_wv_kernel) runs a chain on TWO DPP rows: with HS = (NSTEP + 1) / 2, rows 0 and 1
-// (pair 0) take the first HS positions of chains A and B, rows 2 and 3 (pair 1) the rest and the middle block, every lane
-// with its rows of G in registers: slot s of a lane is the s-th position of its half, the middle block sits in slot HS of
-// pair 1 (both of its rows compute it, row 2 stores it).  Block position -> (row pair, row of the pair = chain, register
-// slot, index of component 0 of its r / x~ inside a block vector, index of its couplings inside ef / en).
-struct WvGresSlot { int pair, row, slot, vidx, eidx; };
-__host__ __device__ inline WvGresSlot wv_gres_slot(int nstep, int pos) {
-  const int hs = (nstep + 1) / 2, npos = 2 * nstep + 2;
-  WvGresSlot s = {-1, -1, -1, -1, -1};
-  if (pos < 0 || pos > 2 * nstep) return s;                       // (2 nstep + 1: the dummy block of idle lanes, no sweep lane)
-  if (pos == nstep) { s.pair = 1; s.row = 0; s.slot = hs; }
-  else {
-    const int chain = pos > nstep ? 1 : 0, st = pos - (chain ? nstep + 1 : 0);
-    s.pair = st >= hs ? 1 : 0; s.row = chain; s.slot = st - (s.pair ? hs : 0);
-  }
-  s.vidx = wv_vidx(npos, pos, 0); s.eidx = pos * 8;
-  return s;
-}
-// out[5] = pair, row, slot, vidx, eidx of block position pos in the NSTEP-step kernel (-1s: no sweep lane holds it)
-extern "C" int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]) {
-  if (!out || nstep <= 0) return SCO_ERR_ARG;
-  const WvGresSlot s = wv_gres_slot(nstep, pos);
-  out[0] = s.pair; out[1] = s.row; out[2] = s.slot; out[3] = s.vidx; out[4] = s.eidx;
-  return SCO_OK;
-}
-
-// int tables, [..][64] lane-minor; offsets in units of 64 ints
-struct WvTab {
-  int pos, hrow, hbrow, hevar, heidx, hepos, hbpos, hjpos, vvar, vrow, vpos, vpk, vpkm, vpkp, vpd, vpm, vpp, xrow, xpos, xpk, total;
-  int lrow, lplo, lphi;           // link slots, NV x NL each, behind everything else (NL = 0: none, `total` as without them)
-};
-// link slot s of variable slot v (the variable is the row's end in block t, its partner the same in-block index of block
-// t + 1): lrow the row, lplo / lphi the CSC positions of A(row, own) and A(row, partner); the partner's place in a block
-// vector is the slot's vpkp
-__host__ __device__ inline WvTab wv_tab_layout(int NS, int NV, int NL = 0) {
-  WvTab t; int o = 0;
-  t.pos = o; o += 1;
-  t.hrow = o; o += NS; t.hbrow = o; o += NS; t.hevar = o; o += NS; t.heidx = o; o += NS; t.hepos = o; o += NS; t.hbpos = o; o += NS;
-  t.hjpos = o; o += NS * 8;
-  t.vvar = o; o += NV; t.vrow = o; o += NV; t.vpos = o; o += NV; t.vpk = o; o += NV; t.vpkm = o; o += NV; t.vpkp = o; o += NV;
-  t.vpd = o; o += NV * 8; t.vpm = o; o += NV; t.vpp = o; o += NV;
-  t.xrow = o; o += 1; t.xpos = o; o += 1; t.xpk = o; o += 1;
-  t.lrow = o; o += NV * NL; t.lplo = o; o += NV * NL; t.lphi = o; o += NV * NL;
-  t.total = o;
-  return t;
-}
-// constants of the termination test, [slot][64] per problem: hinge slot q: 1/E_h, 1/E_b, 1/D_e; variable slot v: 1/D_c,
-// 1/E_0, P(c, c-), P(c, c+), P(c, c), then P(c, block)[8] (read only by problems whose P has entries off these three
-// diagonals: pflag); extra row: 1/E_x.  The scalings themselves (E, D) are formed from the reciprocals when the
-// certificates' norms need them: the fetch of these constants is what a checked iteration costs most
-// (every wavefront of the chip asks for them at the same time).
-__host__ __device__ inline int wv_cst_h(int q) { return 3 * q; }
-__host__ __device__ inline int wv_cst_v(int NS, int v) { return 3 * NS + 13 * v; }
-__host__ __device__ inline int wv_cst_x(int NS, int NV) { return 3 * NS + 13 * NV; }
-// link slot i = v NL + s: 1/E of its row (plans with link rows only)
-__host__ __device__ inline int wv_cst_l(int NS, int NV, int i) { return 3 * NS + 13 * NV + 1 + i; }
-// The four constants of a link slot (its two A entries, l, u) live in registers where the instantiation has room for them,
-// else lane-private in LDS, by the compiler's resource report (profiles/wv_link_rows.md): the 7-wide instantiations hold
-// 256 + ~200 registers without link rows and would spill with 48 more.  In LDS they take the place of the constants of the
-// termination test (qp_admm_wv_kernel, CKG), so that the plan stays within 40 KB.
-__host__ __device__ constexpr bool wv_link_regs(int BS) { return BS != 7; }
 // (v_rcp_f64, one instruction: these reciprocals only scale the norms of the infeasibility tests)
 __device__ __forceinline__ double wv_recip(double x) { return x != 0.0 ? __builtin_amdgcn_rcp(x) : 0.0; }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// host plan
-// ---------------------------------------------------------------------------------------------------------------------
-// Why a pattern without a block structure has none, for the refusal's reason only: the block order is read off P (the
-// smoothing objective couples c with c + bs) and the rows without a slack are judged by it.
-static int wv_why_no_blocks(const QpPlan &pl) {
-  int bs = 0;
-  for (int c = 0; c < pl.n; c++)
-    for (int t = pl.Pp[c]; t < pl.Pp[c + 1]; t++) {
-      const int r = pl.Pi[t];
-      if (r != c && pl.core_of[r] >= 0 && pl.core_of[c] >= 0) bs = std::max(bs, std::abs(pl.core_of[c] - pl.core_of[r]));
-    }
-  if (bs <= 0 || pl.n_c % bs) return WV_WHY_OTHER;
-  int why = WV_WHY_OTHER;
-  for (int i = 0; i < pl.m; i++) {
-    int nc = 0, c0 = -1, c1 = -1; bool slack = false;
-    for (int s = pl.Rp[i]; s < pl.Rp[i + 1]; s++) {
-      const int j = pl.Rj[s];
-      if (pl.elim_of[j] >= 0) { slack = true; continue; }
-      const int c = pl.core_of[j];
-      if (!nc) c0 = c1 = c; else { c0 = std::min(c0, c); c1 = std::max(c1, c); }
-      nc++;
-    }
-    if (slack || nc < 2) continue;
-    if (nc >= 3) return WV_WHY_THREE_CORE;
-    if (c1 / bs == c0 / bs) why = WV_WHY_SAME_BLOCK;
-    else if (c1 % bs != c0 % bs) why = WV_WHY_INDEX;
-    else if (c1 / bs > c0 / bs + 1) why = WV_WHY_FAR_BLOCKS;
-  }
-  return why;
-}
-
-bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
-  wh = WvHost();
-  wh.why = WV_WHY_OTHER;
-  const int n_c = pl.n_c, n_e = pl.n_e, m = pl.m;
-  if (n_e <= 0 || n_c <= 0) return false;
-  // ---- block structure of S: within a block, or between neighbouring blocks at equal in-block index
-  int hb = 0;
-  for (int id = 0; id < pl.nS; id++) hb = std::max(hb, pl.s_a[id] - pl.s_b[id]);
-  auto valid = [&](int bs) {
-    if (bs <= 0 || bs > 8 || n_c % bs) return false;
-    for (int id = 0; id < pl.nS; id++) {
-      const int a = pl.s_a[id], b = pl.s_b[id], ta = a / bs, tb = b / bs;
-      if (!(ta == tb || (ta == tb + 1 && a % bs == b % bs))) return false;
-    }
-    return true;
-  };
-  int bs = 0;
-  if (valid(hb)) bs = hb; else if (valid(n_c)) bs = n_c; else { wh.why = wv_why_no_blocks(pl); return false; }
-  const int nb = n_c / bs;
-  for (int e = 0; e < n_e; e++) if (pl.Pdiag[pl.elim_var[e]] >= 0) return false;      // no P entry on an eliminated variable
-  // ---- rows
-  std::vector<int> h_of(n_e, -1), b_of(n_e, -1), hblk(n_e, -1);
-  std::vector<std::vector<int>> single(n_c), link(n_c);       // link[c]: the rows on c and c + bs, in row order
-  for (int i = 0; i < m; i++) {
-    int ne = 0, nc = 0, e = -1, blk = -1, c0 = -1, c1 = -1; bool one_blk = true;
-    for (int s = pl.Rp[i]; s < pl.Rp[i + 1]; s++) {
-      const int j = pl.Rj[s];
-      if (pl.elim_of[j] >= 0) { ne++; e = pl.elim_of[j]; }
-      else {
-        const int c = pl.core_of[j], t = c / bs;
-        if (nc && t != blk) one_blk = false;
-        if (!nc) c0 = c1 = c; else { c0 = std::min(c0, c); c1 = std::max(c1, c); }
-        blk = t; nc++;
-      }
-    }
-    if (ne == 1 && nc >= 1 && one_blk) { if (h_of[e] >= 0) return false; h_of[e] = i; hblk[e] = blk; }
-    else if (ne == 1 && nc == 0) { if (b_of[e] >= 0) return false; b_of[e] = i; }
-    else if (ne == 0 && nc == 1) single[pl.core_of[pl.Rj[pl.Rp[i]]]].push_back(i);
-    else if (ne == 0 && nc == 2) {
-      // a link row: no slack, one in-block index of two neighbouring blocks; it belongs to the variable of the earlier block
-      if (one_blk) { wh.why = WV_WHY_SAME_BLOCK; return false; }
-      if (c1 % bs != c0 % bs) { wh.why = WV_WHY_INDEX; return false; }
-      if (c1 != c0 + bs) { wh.why = WV_WHY_FAR_BLOCKS; return false; }
-      if (!allow_links) { wh.why = WV_WHY_LINKS_OFF; return false; }
-      if ((int)link[c0].size() >= WV_NL) { wh.why = WV_WHY_THIRD_LINK; return false; }
-      link[c0].push_back(i); wh.n_link++;
-    }
-    else { if (ne == 0 && nc >= 3) wh.why = WV_WHY_THREE_CORE; return false; }
-  }
-  wh.NL = wh.n_link > 0 ? WV_NL : 0;
-  for (int e = 0; e < n_e; e++)
-    if (h_of[e] < 0 || b_of[e] < 0 || pl.Ap[pl.elim_var[e] + 1] - pl.Ap[pl.elim_var[e]] != 2) return false;
-  // ---- single rows.  The variable's own slot takes its LAST single row (the box row: below); xrow[c] is the row it gives to
-  // an extra-row lane, stack[c] the rows it holds in its free link slots
-  int n_extra = 0; bool plain = true;
-  std::vector<int> xrow(n_c, -1);
-  std::vector<std::vector<int>> stack(n_c);
-  for (int c = 0; c < n_c; c++) { if (single[c].size() > 2) plain = false; if (single[c].size() == 2) n_extra++; }
-  if (plain && n_extra <= WV_T) {
-    // at most two single rows per variable and a lane for every second one: the first row of a pair on an extra-row lane
-    for (int c = 0; c < n_c; c++) if (single[c].size() == 2) xrow[c] = single[c][0];
-  } else {
-    // STACKED rows: the rows in front of the last one go into the variable's free link slots, filled from the back, in row
-    // order.  One row may be left over: the variable's first (the place of a pin in the reference's row order), which takes
-    // an extra-row lane.  A variable with two single rows keeps its first one on a lane while lanes last (handed out in
-    // column order, behind the left-over rows), then stacks it.  (A pin that ends up in a slot -- three single rows with both
-    // slots free -- fails the value test, rho_eq: such problems run on the row-local kernel.)
-    if (!allow_links) return false;
-    int n_left = 0;
-    for (int c = 0; c < n_c; c++) {
-      const int k = (int)single[c].size(), free_slots = WV_NL - (int)link[c].size();
-      if (k < 3) continue;
-      if (k - 1 > free_slots + 1) { wh.why = WV_WHY_STACKED; return false; }
-      const int ns = std::min(free_slots, k - 1);
-      stack[c].assign(single[c].end() - 1 - ns, single[c].end() - 1);
-      if (k - 1 > ns) { xrow[c] = single[c][0]; n_left++; }
-    }
-    if (n_left > WV_T) { wh.why = WV_WHY_STACKED; return false; }
-    n_extra = n_left;
-    for (int c = 0; c < n_c; c++) {
-      if (single[c].size() != 2) continue;
-      if (n_extra < WV_T) { xrow[c] = single[c][0]; n_extra++; }
-      else if ((int)link[c].size() < WV_NL) stack[c].push_back(single[c][0]);
-      else { wh.why = WV_WHY_STACKED; return false; }
-    }
-    for (int c = 0; c < n_c; c++) wh.n_stack += (int)stack[c].size();
-  }
-  wh.NL = wh.n_link + wh.n_stack > 0 ? WV_NL : 0;
-  // ---- lanes
-  int lpb = 0;
-  for (int L = 8; L >= 1; L--) if (nb <= 4 * (16 / L)) { lpb = L; break; }
-  if (!lpb) return false;
-  const int bpr = 16 / lpb;
-  std::vector<std::vector<int>> hin(nb);
-  for (int e = 0; e < n_e; e++) hin[hblk[e]].push_back(e);          // elimination order = row order inside a block
-  int maxh = 0;
-  for (auto &v : hin) maxh = std::max(maxh, (int)v.size());
-  const int NS = std::max(1, (maxh + lpb - 1) / lpb), NV = (bs + lpb - 1) / lpb;
-  const int mid = nb / 2;
-  // instantiations <BS, NS, NV, NSTEP>, the smallest that holds the shape first (row slots and padded block steps of a larger one
-  // are executed all the same): <8, 1, 1, 4>, <8, 2, 2, 8>, <8, 2, 2, 10>, and <7, 4, 3, 10> for the 7-DOF x 20 shapes.  A shape that
-  // would need more (e.g. 4-DOF x 24: 3 row slots, 12 steps) stays on the row-local tier: an instantiation with 4 x 4 slots and 16
-  // steps (r04, dropped) held 496 VGPRs and 42 KB of LDS -- three problems per CU at half the row-local kernel's rate
-  // (profiles/r04_tier_choice.txt).
-  if (NS <= 1 && NV <= 1 && mid <= 4) { wh.BS = 8; wh.NS = 1; wh.NV = 1; wh.NSTEP = 4; }
-  else if (NS <= 2 && NV <= 2 && mid <= 8) { wh.BS = 8; wh.NS = 2; wh.NV = 2; wh.NSTEP = 8; }
-  else if (NS <= 2 && NV <= 2 && mid <= 10) { wh.BS = 8; wh.NS = 2; wh.NV = 2; wh.NSTEP = 10; }
-  else if (bs == 7 && NS <= 4 && NV <= 3 && mid <= 10) { wh.BS = 7; wh.NS = 4; wh.NV = 3; wh.NSTEP = 10; }
-  else { wh.why = WV_WHY_SHAPE; return false; }
-  wh.bs = bs; wh.nb = nb; wh.mid = mid; wh.lpb = lpb; wh.n_extra = n_extra;
-  const int NSTEP = wh.NSTEP, lenB = nb - 1 - mid, npos = 2 * NSTEP + 2, dummy = npos - 1;
-  auto pos_of = [&](int t) { return t < mid ? NSTEP - mid + t : t == mid ? NSTEP : 2 * NSTEP + 1 - lenB + (nb - 1 - t); };
-  auto apos = [&](int row, int var) {            // position of A(row, var) in the CSC value array
-    for (int s = pl.Rp[row]; s < pl.Rp[row + 1]; s++) if (pl.Rj[s] == var) return pl.Rpos[s];
-    return -1;
-  };
-  auto ppos = [&](int va, int vb) {              // position of P(va, vb) in the upper-triangular CSC array
-    const int r = std::min(va, vb), c = std::max(va, vb);
-    for (int t = pl.Pp[c]; t < pl.Pp[c + 1]; t++) if (pl.Pi[t] == r) return t;
-    return -1;
-  };
-  const WvTab T = wv_tab_layout(wh.NS, wh.NV, wh.NL);
-  wh.tab.assign((size_t)T.total * 64, -1);
-  auto at = [&](int off, int lane) -> int & { return wh.tab[(size_t)off * 64 + lane]; };
-  for (int l = 0; l < 64; l++) {
-    at(T.pos, l) = dummy;                                           // idle lanes sit on the all-zero dummy block
-    for (int v = 0; v < wh.NV; v++) { at(T.vpk + v, l) = wv_vidx(npos, dummy, v & 7); at(T.vpkm + v, l) = wv_vidx(npos, dummy, 0); at(T.vpkp + v, l) = wv_vidx(npos, dummy, 0); }
-    at(T.xpk, l) = wv_vidx(npos, dummy, 0);
-  }
-  int xl = 0;
-  for (int t = 0; t < nb; t++) {
-    const int base = 16 * (t / bpr) + lpb * (t % bpr), p = pos_of(t);
-    for (int sub = 0; sub < lpb; sub++) at(T.pos, base + sub) = p;
-    for (int r = 0; r < (int)hin[t].size(); r++) {
-      const int e = hin[t][r], l = base + r % lpb, q = r / lpb, ve = pl.elim_var[e];
-      at(T.hrow + q, l) = h_of[e]; at(T.hbrow + q, l) = b_of[e]; at(T.hevar + q, l) = ve; at(T.heidx + q, l) = e;
-      at(T.hepos + q, l) = apos(h_of[e], ve); at(T.hbpos + q, l) = apos(b_of[e], ve);
-      for (int k = 0; k < bs; k++) at(T.hjpos + q * 8 + k, l) = apos(h_of[e], pl.core_var[t * bs + k]);
-    }
-    for (int k = 0; k < bs; k++) {
-      const int l = base + k % lpb, v = k / lpb, c = t * bs + k, var = pl.core_var[c];
-      at(T.vvar + v, l) = var; at(T.vpk + v, l) = wv_vidx(npos, p, k);
-      at(T.vpkm + v, l) = t > 0 ? wv_vidx(npos, pos_of(t - 1), k) : wv_vidx(npos, dummy, 0);
-      at(T.vpkp + v, l) = t + 1 < nb ? wv_vidx(npos, pos_of(t + 1), k) : wv_vidx(npos, dummy, 0);
-      // the variable's own slot takes its LAST single row: the reference appends the bound / trust-region rows behind all
-      // constraint rows (osqp_utils.py:185-189), so that is the box row, which sits on the base rho; an earlier one (a pin:
-      // equality, rho_eq) goes to the general extra-row lanes
-      if (!single[c].empty()) { at(T.vrow + v, l) = single[c].back(); at(T.vpos + v, l) = apos(single[c].back(), var); }
-      for (int k2 = 0; k2 < bs; k2++) at(T.vpd + v * 8 + k2, l) = ppos(var, pl.core_var[t * bs + k2]);
-      at(T.vpm + v, l) = t > 0 ? ppos(var, pl.core_var[(t - 1) * bs + k]) : -1;
-      at(T.vpp + v, l) = t + 1 < nb ? ppos(var, pl.core_var[(t + 1) * bs + k]) : -1;
-      if (xrow[c] >= 0) { at(T.xrow, xl) = xrow[c]; at(T.xpos, xl) = apos(xrow[c], var); at(T.xpk, xl) = wv_vidx(npos, p, k); xl++; }
-      const int nlk = (int)link[c].size();
-      for (int s = 0; s < nlk; s++) {                               // (link[c] is empty in the last block: c + bs does not exist)
-        const int i = v * wh.NL + s, row = link[c][s];
-        at(T.lrow + i, l) = row; at(T.lplo + i, l) = apos(row, var); at(T.lphi + i, l) = apos(row, pl.core_var[c + bs]);
-      }
-      // stacked rows behind them: no partner entry (lphi stays -1, the kernel takes it as coefficient 0), also in the last
-      // block, where the partner's place is the dummy block
-      for (int s = 0; s < (int)stack[c].size(); s++) {
-        const int i = v * wh.NL + nlk + s, row = stack[c][s];
-        at(T.lrow + i, l) = row; at(T.lplo + i, l) = apos(row, var); at(T.lphi + i, l) = -1;
-      }
-    }
-  }
-  // LDS of the ADMM kernel (doubles): G, ef, en, em | r, x~, x, extra | Jacobian rows (unless they live in registers) | partials
-  const bool jreg = WV_JREG && wh.NS * wh.BS <= 28;
-  wh.g_doubles = (size_t)npos * 64 + 2 * (size_t)npos * 8 + 8;
-  // (+ the constants of the termination test, lane-minor: 3 NS + 5 NV + 1 slots of 64 doubles)
-  wh.lds_doubles = wh.g_doubles + 4 * (size_t)npos * 8 + (jreg ? 0 : (size_t)wh.NS * 512) + (size_t)npos * lpb * 8 + (size_t)(3 * wh.NS + 5 * wh.NV + 1) * 64;
-  wh.cst_slots = 3 * wh.NS + 13 * wh.NV + 1;
-  if (wh.NL) {
-    // link rows: one more block vector (the partner's share of the right-hand side); where the instantiation keeps the
-    // slots' four constants in lane-private LDS, they take the place of the constants of the termination test
-    const int nl = wh.NV * wh.NL;
-    wh.lds_doubles += (size_t)npos * 8;
-    if (!wv_link_regs(wh.BS)) wh.lds_doubles = wh.lds_doubles - (size_t)(3 * wh.NS + 5 * wh.NV + 1) * 64 + (size_t)nl * 4 * 64;
-    wh.cst_slots += nl;
-  }
-  wh.lds_bytes = wh.lds_doubles * sizeof(double);
-  // the tier pays only with FOUR problems per CU (one wavefront per SIMD): 40 KB each at most
-  wh.per_cu = SCO_WV_PER_CU;
-  const bool fits = wh.lds_bytes <= 40 * 1024;
-  wh.why = fits ? WV_OK : WV_WHY_LDS;
-  return fits;
-}
 
 int wv_upload(const WvHost &wh, int batch, int n, int m, std::vector<void *> &allocs, WvDev &wd) {
   void *p = nullptr;
@@ -717,7 +420,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   // The lane's Jacobian rows: constants of the solve, read twice per iteration.  In REGISTERS where the instantiation has
   // room (NS x BS <= 28 doubles: every instantiation built today), else lane-private in LDS: the kernel is bound by the CU's LDS
   // pipe (four wavefronts share it), and these rows were a third of a wavefront's LDS bytes per iteration.
-  constexpr bool JREG = WV_JREG && NS * BS <= 28;
+  constexpr bool JREG = wv_jreg(NS, BS);
   constexpr int oG = 0, oEF = oG + NPOS * 64, oEN = oEF + NPOS * 8, oEM = oEN + NPOS * 8, oR = oEM + 8, oXT = oR + NPOS * 8,
                 oXC = oXT + NPOS * 8, oEX = oXC + NPOS * 8, oLK = oEX + NPOS * 8, oJ = oLK + (LNK > 0 ? NPOS * 8 : 0),
                 oPART = oJ + (JREG ? 0 : NS * 512);
@@ -764,16 +467,16 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
 #pragma unroll
     for (int q = 0; q < NS; q++)
 #pragma unroll
-      for (int k = 0; k < 3; k++) ckl[(3 * q + k) * 64] = cstg0[(wv_cst_h(q) + k) * 64];
+      for (int k = 0; k < 3; k++) ckl[(wv_ck_h(q) + k) * 64] = cstg0[(wv_cst_h(q) + k) * 64];
 #pragma unroll
     for (int v = 0; v < NV; v++)
 #pragma unroll
-      for (int k = 0; k < 5; k++) ckl[(3 * NS + 5 * v + k) * 64] = cstg0[(wv_cst_v(NS, v) + k) * 64];
-    ckl[(3 * NS + 5 * NV) * 64] = cstg0[wv_cst_x(NS, NV) * 64];
+      for (int k = 0; k < 5; k++) ckl[(wv_ck_v(NS, v) + k) * 64] = cstg0[(wv_cst_v(NS, v) + k) * 64];
+    ckl[wv_ck_x(NS, NV) * 64] = cstg0[wv_cst_x(NS, NV) * 64];
   }
-#define CKH(q, k) (CKG ? wv_opaque(cstg0)[(wv_cst_h(q) + (k)) * 64] : ckl[(3 * (q) + (k)) * 64])
-#define CKV(v, k) (CKG ? wv_opaque(cstg0)[(wv_cst_v(NS, v) + (k)) * 64] : ckl[(3 * NS + 5 * (v) + (k)) * 64])
-#define CKX (CKG ? wv_opaque(cstg0)[wv_cst_x(NS, NV) * 64] : ckl[(3 * NS + 5 * NV) * 64])
+#define CKH(q, k) (CKG ? wv_opaque(cstg0)[(wv_cst_h(q) + (k)) * 64] : ckl[(wv_ck_h(q) + (k)) * 64])
+#define CKV(v, k) (CKG ? wv_opaque(cstg0)[(wv_cst_v(NS, v) + (k)) * 64] : ckl[(wv_ck_v(NS, v) + (k)) * 64])
+#define CKX (CKG ? wv_opaque(cstg0)[wv_cst_x(NS, NV) * 64] : ckl[wv_ck_x(NS, NV) * 64])
   // (1/E of a link slot's row comes from global memory at the checked iteration in every instantiation, as the dense P
   // constants do)
 #define CKL(i) wv_opaque(cstg0)[wv_cst_l(NS, NV, i) * 64]

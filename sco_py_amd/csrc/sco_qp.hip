@@ -60,7 +60,6 @@ extern "C" void sco_qp_default_settings(sco_qp_settings *s) {
 // --------------------------------------------------------------------------
 // device helpers
 // --------------------------------------------------------------------------
-#define NWAVE (SCO_BLOCK / 64)
 
 __host__ __device__ __forceinline__ size_t tri_idx(int i, int j) {   // packed lower, j <= i
   return (size_t)i * (i + 1) / 2 + j;
@@ -483,10 +482,6 @@ struct AdmmLds {
   int *w;
 };
 
-__host__ __device__ inline size_t admm_lds_doubles(int n, int m, int nnzA, int n_e, int n_c, int ncpl) {
-  return (size_t)nnzA + n + 2 * (size_t)m + m + n + 2 * (size_t)m + m + n + n_e + 2 * (size_t)n_c + n_e + ncpl + m + n + NWAVE * 8;
-}
-
 // How qp_admm_kernel reaches rows, columns and dot products for osqp_check (sco_admm_check.h): thread t owns rows and
 // columns t, t + SCO_BLOCK, ...; CSR / CSC walks over the iterates in LDS
 struct AdmmOps {
@@ -720,60 +715,7 @@ __global__ void qp_rho_init_kernel(RhoInitArgs a) {
 // --------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------
-static const size_t LDS_CAP = 160 * 1024;     // LDS of a CU
-
-static size_t setup_lds_doubles(const QpPlan &pl) {
-  return (size_t)pl.nnzP + pl.nnzA + 2 * (size_t)pl.n + pl.m + pl.n + pl.m + pl.ncpl + NWAVE * 2 +
-         (size_t)pl.n_c * (pl.n_c + 1) / 2;
-}
-
-// Step 1 of sco_qp_create: everything that is decided about the handle, from the pattern and the switches alone.  No HIP
-// call: sco_debug_plan_tiers runs it on a machine without a GPU.
-static int qp_choose_tiers(int n, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai, const QpCreateEnv &env,
-                           QpTiers &t) {
-  t.factor_cholesky = env.factor_cholesky;
-  int rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, env.no_elim ? 0 : 1, t.plan);
-  if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
-  const QpPlan &pl = t.plan;
-  t.lds_setup = setup_lds_doubles(pl) * sizeof(double);
-  t.lds_admm = admm_lds_doubles(n, m, pl.nnzA, pl.n_e, pl.n_c, pl.ncpl) * sizeof(double) + (size_t)m * sizeof(int);
-  if (t.lds_setup > LDS_CAP || t.lds_admm > LDS_CAP || pl.n_c > SCO_BLOCK || env.force_big) {
-    // working set beyond a CU's LDS: the global-memory tier (sco_qp_big.hip)
-    bool ok_big = pl.n_c <= 1024 && big_plan_build(pl, t.big);
-    if (!ok_big && !env.no_elim) {
-      // the global-memory kernels keep an eliminated variable and its (at most two) rows in one thread:
-      // send variables with more rows to the core and analyse again
-      rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, 2, t.plan);
-      if (rc != 0) { sco_set_error("sco_qp_create: malformed sparsity pattern"); return SCO_ERR_ARG; }
-      t.big = BigHost();
-      ok_big = pl.n_c <= 1024 && big_plan_build(pl, t.big);
-    }
-    if (!ok_big) {
-      char buf[256];
-      snprintf(buf, sizeof buf, "sco_qp_create: pattern not supported (setup %zu B, admm %zu B of LDS, core %d)",
-               t.lds_setup, t.lds_admm, pl.n_c);
-      sco_set_error(buf); return SCO_ERR_CAPACITY;
-    }
-    t.use_big = true;
-    t.use_bt = !env.no_bt && bt_plan_build(pl, t.big, t.bt);
-    return SCO_OK;
-  }
-  // on-chip: the first ADMM kernel whose plan fits the pattern is the one this handle runs
-  int CW = 0, RW = 0, PX = 0;
-  if (!env.no_rl && rl_plan_build(pl, t.rl)) {
-    t.kern = QP_K_RL;
-    // wavefront tier (one wavefront per problem, block-tridiagonal core solve): patterns of trajectory penalty QPs; it
-    // needs the row-local kernel beside it for problems whose values leave the penalty-QP structure, and the Gauss-Jordan
-    // inversion.  The opt-in extensions (warm start, adaptive rho) run on it too; rows that link two neighbouring timesteps
-    // (velocity limits) are allowed, without adaptive rho
-    t.use_wv = !env.factor_cholesky && !env.no_wv && wv_plan_build(pl, t.wv, true);
-  } else if (!env.no_reg && reg_caps_for(pl, &CW, &RW, &PX) && reg_plan_build(pl, CW, RW, PX, t.reg)) {
-    t.kern = QP_K_REG;
-  } else if (!env.no_fast && fast_plan_build(pl, t.fast)) {
-    t.kern = QP_K_FAST;
-  }
-  return SCO_OK;
-}
+static const size_t LDS_CAP = SCO_LDS_CAP;    // LDS of a CU
 
 static int qp_alloc_upload(sco_qp *qp, int device, int batch, hipStream_t stream);
 
@@ -791,7 +733,9 @@ int sco_qp_create_on_stream(int device, int batch, int n, int m, const int *Pp, 
   SCO_ON_DEVICE(device);
   sco_qp *qp = new sco_qp();
   qp->device = device;
-  int rc = qp_choose_tiers(n, m, Pp, Pi, Ap, Ai, qp_create_env(), *qp);
+  std::string err;
+  int rc = qp_choose_tiers(n, m, Pp, Pi, Ap, Ai, qp_create_env(), *qp, &err);       // (qp_tier_choice.cpp)
+  if (rc) sco_set_error(err);
   if (!rc) rc = qp_alloc_upload(qp, device, batch, stream);
   if (rc) { sco_qp_destroy(qp); return rc; }      // frees whatever had been allocated
   *out = qp;
@@ -1141,109 +1085,15 @@ extern "C" int sco_qp_last_timing(const sco_qp *qp, double ms[2]) {
   return SCO_OK;
 }
 
-// --------------------------------------------------------------------------
-// Host-only debug view of the symbolic analysis (no HIP call): lets the CPU
-// test-suite check the plans against a NumPy emulation of the kernels.
-// sizes[16]: n_e, n_c, ncpl, nS, len(cp_row), len(sa_row), len(ss_k1), nnzFull
-// --------------------------------------------------------------------------
-static QpPlan g_dbg_plan;
-extern "C" int sco_debug_plan_build(int n, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
-                                    int allow_elim, int *sizes) {
-  int rc = qp_plan_build(n, m, Pp, Pi, Ap, Ai, allow_elim, g_dbg_plan);
-  if (rc) return SCO_ERR_ARG;
-  const QpPlan &p = g_dbg_plan;
-  sizes[0] = p.n_e; sizes[1] = p.n_c; sizes[2] = p.ncpl; sizes[3] = p.nS;
-  sizes[4] = (int)p.cp_row.size(); sizes[5] = (int)p.sa_row.size(); sizes[6] = (int)p.ss_k1.size();
-  sizes[7] = (int)p.Fi.size();
-  return SCO_OK;
-}
-// Host-only: would the pattern last given to sco_debug_plan_build land on the row-local tier, and with what shape?
-// info[0] fits, [1] CW (value slots per column = 2 x operand pairs), [2] TR, [3] TC, [4] dynamic LDS bytes, [5] closed plan,
-// [6] 1 = aligned closed plan (one barrier per iteration), 2 = 8 column groups of the W tile with the open assignment,
-// [7] row slots per thread
-extern "C" int sco_debug_rl_plan(int *info) {
-  RlHost rh;
-  const bool ok = rl_plan_build(g_dbg_plan, rh);
-  info[0] = ok ? 1 : 0; info[1] = rh.CW; info[2] = rh.TR; info[3] = rh.TC; info[4] = (int)rh.lds_bytes; info[5] = rh.merged ? 1 : 0; info[6] = rh.aligned ? 1 : rh.lay8 ? 2 : 0; info[7] = rh.NS;
-  return SCO_OK;
-}
-// Host-only: would that pattern land on the wavefront tier with the link-free plan?  info[0] fits, [1] block order,
-// [2] blocks, [3] lanes per block, [4] instantiation BS, [5] NS, [6] NV, [7] NSTEP, [8] LDS bytes, [9] second single rows
-static bool dbg_wv_plan(bool allow_links, int *info, WvHost &wh) {
-  const bool ok = wv_plan_build(g_dbg_plan, wh, allow_links);
-  info[0] = ok ? 1 : 0; info[1] = wh.bs; info[2] = wh.nb; info[3] = wh.lpb; info[4] = wh.BS; info[5] = wh.NS; info[6] = wh.NV;
-  info[7] = wh.NSTEP; info[8] = (int)wh.lds_bytes; info[9] = wh.n_extra;
-  return ok;
-}
-extern "C" int sco_debug_wv_plan(int *info) {
-  WvHost wh;
-  dbg_wv_plan(false, info, wh);
-  return SCO_OK;
-}
-// ... and with the plan a handle builds, link rows allowed: the ten fields above, then [10] link rows, [11] link slots per
-// variable slot (0: no link rows), [12] problems per CU, [13] why the plan was refused (WvWhy: 0 accepted, 1 other,
-// 2 link rows not allowed, 3 a third link row on one pair, 4 two core variables of one block without a slack, 5 blocks that
-// are not neighbours, 6 different in-block indices, 7 three or more core variables, 8 LDS, 9 no instantiation for the shape)
-extern "C" int sco_debug_wv_link_plan(int *info) {
-  WvHost wh;
-  dbg_wv_plan(true, info, wh);
-  info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why;
-  return SCO_OK;
-}
-// ... the same fourteen fields (why: also 10 = single rows of a variable beyond its free link slots or beyond the extra-row
-// lanes), then [14] stacked rows: single rows held in a variable slot's link slots with an empty partner
-extern "C" int sco_debug_wv_stack_plan(int *info) {
-  WvHost wh;
-  dbg_wv_plan(true, info, wh);
-  info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why; info[14] = wh.n_stack;
-  return SCO_OK;
-}
-// Host-only: the structured global-memory plan of that pattern.  info[0] fits, [1] block order, [2] blocks, [3] block normal
-// matrices on the matrix cores, [4] why not (BtHost::mf_why), [5] LDS bytes
-extern "C" int sco_debug_bt_plan(int *info) {
-  BigHost bh; BtHost th;
-  const bool ok = g_dbg_plan.n_c <= 1024 && big_plan_build(g_dbg_plan, bh) && bt_plan_build(g_dbg_plan, bh, th);
-  info[0] = ok ? 1 : 0; info[1] = th.bs; info[2] = th.nb; info[3] = th.use_mfma ? 1 : 0; info[4] = th.mf_why; info[5] = (int)th.lds_bytes;
-  return SCO_OK;
-}
-// Which ADMM tiers a handle RUNS: bit 0 row-local, 1 register-offset, 2 sliced-ELL (at most one of the three: the handle's
-// on-chip kernel; none = the generic kernel), 3 global memory, 4 its structured form, 5 wavefront tier beside the row-local
-// kernel, 6 the structured form builds its block normal matrices on the matrix cores (MFMA).  (Bits 1 and 2 said "holds the
-// plan" while handles still built plans they could never launch.)
-static int qp_tier_mask(const QpTiers &t) {
-  return (t.kern == QP_K_RL ? 1 : 0) | (t.kern == QP_K_REG ? 2 : 0) | (t.kern == QP_K_FAST ? 4 : 0) | (t.use_big ? 8 : 0) |
-         (t.use_bt ? 16 : 0) | (t.use_wv ? 32 : 0) | ((t.use_bt && t.bt.use_mfma) ? 64 : 0);
-}
+// Which ADMM tiers this handle runs (the bits: qp_tier_mask, qp_tier_choice.cpp).  The host-only debug views -- plans and
+// tier choice of a pattern, without a handle -- are qp_debug.cpp.
 extern "C" int sco_debug_qp_tiers(const sco_qp *qp) {
   if (!qp) return SCO_ERR_ARG;
   return qp_tier_mask(*qp);
-}
-// Host-only: the mask sco_debug_qp_tiers would give for a handle created now -- under the SCO_QP_* switches as they stand --
-// from the pattern last given to sco_debug_plan_build (whatever allow_elim was passed there)
-extern "C" int sco_debug_plan_tiers(int *mask) {
-  const QpPlan &p = g_dbg_plan;
-  if (!mask || p.n <= 0) return SCO_ERR_ARG;
-  QpTiers t;
-  SCO_TRY(qp_choose_tiers(p.n, p.m, p.Pp.data(), p.Pi.data(), p.Ap.data(), p.Ai.data(), qp_create_env(), t));
-  *mask = qp_tier_mask(t);
-  return SCO_OK;
 }
 // Iterations run by the wavefront kernel on this handle since the counter was last reset (only the SQP layer resets it): a
 // test reads it before and after a solve to see which problems that kernel really took.  0 on a handle without the tier.
 extern "C" int sco_debug_qp_wv_iters(const sco_qp *qp, unsigned long long *out) {
   if (!qp || !out) return SCO_ERR_ARG;
   return sco_qp_wv_iters(qp, out);
-}
-extern "C" int sco_debug_plan_get(const char *name, int *out, int cap) {
-  const QpPlan &p = g_dbg_plan;
-  const std::vector<int> *v = nullptr;
-#define F(x) if (!strcmp(name, #x)) v = &p.x;
-  F(Rp) F(Rj) F(Rpos) F(Fp) F(Fi) F(Fpos) F(Pdiag) F(elim_var) F(core_var) F(elim_of) F(core_of)
-  F(e_ptr) F(pair_core) F(pair_elim) F(cp_ptr) F(cp_row) F(cp_pa) F(cp_pe) F(a_ptr) F(a_pair)
-  F(s_a) F(s_b) F(s_ppos) F(sa_ptr) F(sa_row) F(sa_pa) F(sa_pb) F(ss_ptr) F(ss_k1) F(ss_k2) F(ss_e)
-#undef F
-  if (!v) return SCO_ERR_ARG;
-  if ((int)v->size() > cap) return SCO_ERR_CAPACITY;
-  std::copy(v->begin(), v->end(), out);
-  return (int)v->size();
 }

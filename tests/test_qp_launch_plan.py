@@ -1,4 +1,4 @@
-"""Tier choice and launch planning of the QP layer (csrc/qp_tier.cpp and qp_choose_tiers of csrc/sco_qp.hip, through
+"""Tier choice and launch planning of the QP layer (csrc/qp_tier.cpp and qp_choose_tiers of csrc/qp_tier_choice.cpp, through
 sco_debug_qp_launch_plan and sco_debug_plan_tiers): host arithmetic only.
 
 The numbers are those of the 256-CU part: a wavefront launch needs 704 problems (2.75 per CU)."""

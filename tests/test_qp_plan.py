@@ -115,7 +115,7 @@ def test_malformed_patterns_are_rejected():
     ("velocity + joint limits", dict(vel_limit=0.3, joint_limit=0.2), 12),
     ("reach + velocity limits", dict(reach=True, vel_limit=0.3), 16)])
 def test_which_device_families_land_on_the_row_local_tier(name, kw, cw):
-    """Host-side plan of the fastest ADMM tier (csrc/sco_admm_rl.hip: rl_plan_build) for the penalty QP of every device
+    """Host-side plan of the fastest ADMM tier (csrc/rl_plan.cpp: rl_plan_build) for the penalty QP of every device
     family at 7-DOF x 20: gather-dots take operands in aligned pairs; CW = 12: a column thread <= 6 pairs, a row <= 4, two
     row slots per thread; 16 (wide): 8 / 5; 20: the three-slot instantiation (10 / 5, up to 1536 rows) that velocity + joint
     limits (1100 rows) needed until r03.  r03: a column's pairs are split over two neighbouring lanes (owner + helper), so the 8 pairs
@@ -151,7 +151,7 @@ def test_which_device_families_land_on_the_row_local_tier(name, kw, cw):
     ("velocity limits", dict(vel_limit=0.3), (0,)), ("reach", dict(reach=True), (0,)), ("joint limits", dict(joint_limit=0.2), (0,)),
     ("span-2 program", dict(d=2, T=8, K=1, program=True, variant="sweep"), (0,))])
 def test_which_penalty_qps_land_on_the_wavefront_tier(name, kw, want):
-    """Host-side plan of the wavefront tier (csrc/sco_admm_wv.hip: wv_plan_build): block-tridiagonal core with diagonal
+    """Host-side plan of the wavefront tier (csrc/wv_plan.cpp: wv_plan_build): block-tridiagonal core with diagonal
     couplings, every hinge row inside one timestep block with its own slack, at most two single rows per core variable.
     info = fits, block order, blocks, lanes per block, instantiation <BS, NS, NV, NSTEP>.  Rows on two timesteps (velocity
     limits, span-2 blocks), abs rows with a core slack (reach) and three single rows per variable (joint limits) stay on
@@ -186,7 +186,7 @@ def test_which_penalty_qps_land_on_the_wavefront_tier(name, kw, want):
 def test_which_structured_plans_form_their_blocks_on_the_matrix_cores(name, kw, want, monkeypatch):
     """r04 (N1): the structured global-memory plan forms the hinge-row part of its diagonal blocks with
     v_mfma_f64_16x16x4 when the block order is 12 .. 16 and every entry of a block sums over the same run of hinge rows
-    (csrc/sco_qp_big.hip bt_plan_build); SCO_QP_NO_MFMA=1 switches it off.  info: fits, block order, blocks, MFMA, why not."""
+    (csrc/big_plan.cpp bt_plan_build); SCO_QP_NO_MFMA=1 switches it off.  info: fits, block order, blocks, MFMA, why not."""
     if isinstance(kw, dict):
         from oracle import arm_family as af
         from oracle import sco_ref as sr

@@ -1,4 +1,4 @@
-"""The tiers a live handle runs are the ones the host-only chooser names (qp_choose_tiers, csrc/sco_qp.hip): sco_debug_qp_tiers
+"""The tiers a live handle runs are the ones the host-only chooser names (qp_choose_tiers, csrc/qp_tier_choice.cpp): sco_debug_qp_tiers
 of a handle = sco_debug_plan_tiers of its pattern, under every route of tests/test_qp_launch_plan.py.  Handles are created
 and closed; only the last case solves."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """The wavefront ADMM tier at the edges of its lane and block layout, without a GPU: the host plan
-(csrc/sco_admm_wv.hip: wv_plan_build -- which instantiation, how many lanes per block, which shapes are refused) for the
+(csrc/wv_plan.cpp: wv_plan_build -- which instantiation, how many lanes per block, which shapes are refused) for the
 patterns of tests/wv_cases.py, and the oracle's own verdict on every batch that tests/test_wavefront_edges_gpu.py solves
 on the device: a comparison on a problem that stops on max_iter without being meant to would pin much less."""
 import ctypes as C

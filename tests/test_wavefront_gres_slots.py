@@ -1,4 +1,4 @@
-"""The slot mapping of the G-resident sweep of the wavefront ADMM tier (csrc/sco_admm_wv.hip: wv_gres_slot, through
+"""The slot mapping of the G-resident sweep of the wavefront ADMM tier (csrc/layout_wv.h: wv_gres_slot, through
 sco_debug_wv_gres_slot), without a GPU: which DPP row pair runs which block position, in which register slot, and where the
 position's right-hand side / x~ and couplings sit in LDS.  For every NSTEP the tier builds and every horizon it serves."""
 import ctypes as C
@@ -18,7 +18,7 @@ def slot(nstep, pos):
 
 
 def wv_vidx(npos, pos, k):
-    """csrc/sco_admm_wv.hip: wv_vidx (block vectors are stored piece-major)."""
+    """csrc/layout_wv.h: wv_vidx (block vectors are stored piece-major)."""
     return (k >> 1) * 2 * npos + 2 * pos + (k & 1)
 
 

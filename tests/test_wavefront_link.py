@@ -1,4 +1,4 @@
-"""Link rows of the wavefront ADMM tier (csrc/sco_admm_wv.hip: rows on one in-block index of two neighbouring timesteps,
+"""Link rows of the wavefront ADMM tier (csrc/sco_admm_wv.hip, plan: csrc/wv_plan.cpp; rows on one in-block index of two neighbouring timesteps,
 i.e. velocity limits), without a GPU: the host plan of the patterns of tests/wv_link_cases.py through
 sco_debug_wv_link_plan, the refusals and their reasons, the launch planner's rule for adaptive rho, and the oracle's own
 verdict on every batch that tests/test_wavefront_link_gpu.py solves on the device."""

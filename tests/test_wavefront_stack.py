@@ -1,4 +1,4 @@
-"""Stacked rows of the wavefront ADMM tier (csrc/sco_admm_wv.hip: single rows of a core variable other than its last one,
+"""Stacked rows of the wavefront ADMM tier (csrc/sco_admm_wv.hip, plan: csrc/wv_plan.cpp; single rows of a core variable other than its last one,
 held in the variable slot's free link slots with an empty partner, i.e. joint limits), without a GPU: the host plan of the
 patterns of tests/wv_stack_cases.py through sco_debug_wv_stack_plan, the counts of stacked and extra-lane rows worked out
 from the assignment rule, the plans of the patterns the tier took before, the refusals, the launch planner's rule for
