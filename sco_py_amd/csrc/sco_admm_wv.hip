@@ -65,6 +65,13 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #ifndef WV_ROWS_EARLY
 #define WV_ROWS_EARLY 1       // 0 = the row phase reads its partial sums behind the core-variable loop, as before (scripts/build_ablate.py wv:WV_ROWS_EARLY=0)
 #endif
+// the sweep's issue slots (profiles/wv_sweep_slots.md; each 0 = the form of before, scripts/build_ablate.py wv:<NAME>=0)
+#ifndef WV_MV_INIT
+#define WV_MV_INIT 1          // wv_matvec: the accumulators' initialisations inside the chain's statement, as its wait states
+#endif
+#ifndef WV_HANDOVER
+#define WV_HANDOVER 1         // lane-swap hand-overs of the sweeps: the swap's two operands chosen so that no select and no copy follows
+#endif
 #if WV_VARIANT == 1
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
 #endif
@@ -145,6 +152,35 @@ __device__ __forceinline__ double wv_wred(double v) {
 }
 __device__ __forceinline__ double wv_wmax(double v) { return wv_wred<true>(v); }
 __device__ __forceinline__ double wv_wsum(double v) { return wv_wred<false>(v); }
+// Both register halves of two doubles through v_permlane16_swap (W = 16: the odd DPP rows of a change places with the even
+// rows of b, row 1 with row 0 and row 3 with row 2) or v_permlane32_swap (W = 32: the upper 32 lanes of a with the lower 32
+// of b).  The hand-overs of the sweeps (WV_HANDOVER) pick a and b so that the swapped registers ARE what the next step needs:
+// a copy of both halves in front of each swap, two selects per half behind it and the wait states between were 29 issue
+// slots of the 7-wide iteration.
+template <int W>
+__device__ __forceinline__ void wv_swap(double &a, double &b) {
+  const unsigned al = (unsigned)__double2loint(a), ah = (unsigned)__double2hiint(a), bl = (unsigned)__double2loint(b), bh = (unsigned)__double2hiint(b);
+  const wv_u2 lo = W == 16 ? __builtin_amdgcn_permlane16_swap(al, bl, false, false) : __builtin_amdgcn_permlane32_swap(al, bl, false, false);
+  const wv_u2 hi = W == 16 ? __builtin_amdgcn_permlane16_swap(ah, bh, false, false) : __builtin_amdgcn_permlane32_swap(ah, bh, false, false);
+  a = __hiloint2double((int)hi.x, (int)lo.x); b = __hiloint2double((int)hi.y, (int)lo.y);
+}
+// The two chains meet: a = b = the last forward vector of the lane's chain (even rows chain A, odd rows chain B).  Behind
+// the swap a holds chain A's vector on EVERY row (the even rows kept their own, the odd rows got the even rows') and b chain
+// B's: the operands of the middle block as they are.  (Before: vother = chain ? a : b, then vA = chain ? vother : vlast and
+// vB = chain ? vlast : vother -- four selects per register half that pick, on every row, exactly these two registers.)
+template <bool DIRECT>
+__device__ __forceinline__ void wv_meet(double vlast, int chain, double &vA, double &vB) {
+  if (DIRECT) {
+    vA = vlast; vB = vlast;
+    wv_swap<16>(vA, vB);
+  } else {
+    const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(vlast), (unsigned)__double2loint(vlast), false, false);
+    const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(vlast), (unsigned)__double2hiint(vlast), false, false);
+    // .x: odd rows now hold the even rows' values; .y: even rows now hold the odd rows' values
+    const double vother = chain ? __hiloint2double((int)hi.x, (int)lo.x) : __hiloint2double((int)hi.y, (int)lo.y);
+    vA = chain ? vother : vlast; vB = chain ? vlast : vother;
+  }
+}
 // the limit of upper_is_infinite / lower_is_infinite and osqp_row_leaves_cone (sco_admm_check.h): keep them one value
 #define WV_BIG (SCO_INFTY * SCO_MIN_SCALING)
 
@@ -275,6 +311,7 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // ADMM kernel
 // ---------------------------------------------------------------------------------------------------------------------
+
 __device__ __forceinline__ double wv_min(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double wv_max(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
@@ -290,36 +327,51 @@ __device__ __forceinline__ WvRow<BS> wv_row(const double *p, const double *pd) {
   return r;
 }
 
-template <int BS>
-__device__ __forceinline__ double wv_matvec(double acc, double w, const WvRow<BS> &g) {
+// The chain's text.  Operands of every statement that uses it: %0, %1 the two accumulators, %2 the broadcast vector w, %3..%9
+// the row of G (WV_G7), %10 its eighth entry where BS is 8.
+#define WV_DPP_STEP(acc, g, k) "v_fmac_f64_dpp " acc ", %2, " g " row_newbcast:" #k " row_mask:0xf bank_mask:0xf\n\t"
+#define WV_DPP_CHAIN7 WV_DPP_STEP("%0", "%3", 0) WV_DPP_STEP("%1", "%4", 1) WV_DPP_STEP("%0", "%5", 2) WV_DPP_STEP("%1", "%6", 3) \
+                      WV_DPP_STEP("%0", "%7", 4) WV_DPP_STEP("%1", "%8", 5) WV_DPP_STEP("%0", "%9", 6)
+#define WV_G7 "v"(g0.x), "v"(g0.y), "v"(g1.x), "v"(g1.y), "v"(g2.x), "v"(g2.y), "v"(g3.x)
+
+// ZERO: the sum starts from 0 (forward steps, the middle block), else from `init` (backward steps: the forward vector)
+// INIT: the initialisations inside the statement (wv_slots bit 0), else in front of it with s_nop 1 as the wait states
+template <int BS, bool ZERO, bool INIT>
+__device__ __forceinline__ double wv_matvec(double init, double w, const WvRow<BS> &g) {
   const d2 g0 = g.a, g1 = g.b, g2 = g.c, g3 = g.d;
   // two accumulators: a dependent v_fmac_f64_dpp issues every 8.5 cycles, two interleaved chains every 6.5
   // (scripts/microbench/wave_cost.hip).  The WHOLE chain sits in one asm statement behind the wait states its first
   // broadcast needs: as separate statements the scheduler was free to put a VALU write of w directly in front of a later
   // broadcast (seen as wrong results of one build, r04, when only the first pair was tied together), and the hazard
   // recogniser does not look into inline assembly.
-  double acc2 = 0.0;
+  // The two wait states ARE the accumulators' initialisations (WV_MV_INIT): a lone wavefront pays an issue slot for an
+  // s_nop as for any instruction, and the two v_mov_b64 the chain needs anyway covered nothing where the compiler put them, in
+  // front of the write of w.  Inside the statement, whoever wrote w last, two VALU instructions stand between that write
+  // and the first broadcast read.  The accumulators are written before the inputs are read: early-clobber outputs.
 #if WV_VARIANT == 1
+  double acc = ZERO ? 0.0 : init, acc2 = 0.0;
   WV_FMAC_DPP(acc, w, g0.x, 0); WV_FMAC_DPP(acc2, w, g0.y, 1);
   WV_FMAC_DPP(acc, w, g1.x, 2); WV_FMAC_DPP(acc2, w, g1.y, 3);
   WV_FMAC_DPP(acc, w, g2.x, 4); WV_FMAC_DPP(acc2, w, g2.y, 5); WV_FMAC_DPP(acc, w, g3.x, 6);
   if (BS > 7) WV_FMAC_DPP(acc2, w, g3.y, 7);
 #else
-#define WV_DPP_STEP(acc, g, k) "v_fmac_f64_dpp " acc ", %2, " g " row_newbcast:" #k " row_mask:0xf bank_mask:0xf\n\t"
-  if (BS > 7)
-    asm("s_nop 1\n\t"
-        WV_DPP_STEP("%0", "%3", 0) WV_DPP_STEP("%1", "%4", 1) WV_DPP_STEP("%0", "%5", 2) WV_DPP_STEP("%1", "%6", 3)
-        WV_DPP_STEP("%0", "%7", 4) WV_DPP_STEP("%1", "%8", 5) WV_DPP_STEP("%0", "%9", 6) WV_DPP_STEP("%1", "%10", 7)
-        : "+v"(acc), "+v"(acc2) : "v"(w), "v"(g0.x), "v"(g0.y), "v"(g1.x), "v"(g1.y), "v"(g2.x), "v"(g2.y), "v"(g3.x), "v"(g3.y));
-  else
-    asm("s_nop 1\n\t"
-        WV_DPP_STEP("%0", "%3", 0) WV_DPP_STEP("%1", "%4", 1) WV_DPP_STEP("%0", "%5", 2) WV_DPP_STEP("%1", "%6", 3)
-        WV_DPP_STEP("%0", "%7", 4) WV_DPP_STEP("%1", "%8", 5) WV_DPP_STEP("%0", "%9", 6)
-        : "+v"(acc), "+v"(acc2) : "v"(w), "v"(g0.x), "v"(g0.y), "v"(g1.x), "v"(g1.y), "v"(g2.x), "v"(g2.y), "v"(g3.x));
-#undef WV_DPP_STEP
+  double acc = ZERO ? 0.0 : init, acc2 = 0.0;
+  if (!INIT) {
+    if (BS > 7) asm("s_nop 1\n\t" WV_DPP_CHAIN7 WV_DPP_STEP("%1", "%10", 7) : "+v"(acc), "+v"(acc2) : "v"(w), WV_G7, "v"(g3.y));
+    else asm("s_nop 1\n\t" WV_DPP_CHAIN7 : "+v"(acc), "+v"(acc2) : "v"(w), WV_G7);
+  } else if (BS > 7) {
+    if (ZERO) asm("v_mov_b64 %1, 0\n\tv_mov_b64 %0, 0\n\t" WV_DPP_CHAIN7 WV_DPP_STEP("%1", "%10", 7) : "=&v"(acc), "=&v"(acc2) : "v"(w), WV_G7, "v"(g3.y));
+    else asm("v_mov_b64 %1, 0\n\tv_mov_b64 %0, %11\n\t" WV_DPP_CHAIN7 WV_DPP_STEP("%1", "%10", 7) : "=&v"(acc), "=&v"(acc2) : "v"(w), WV_G7, "v"(g3.y), "v"(init));
+  } else {
+    if (ZERO) asm("v_mov_b64 %1, 0\n\tv_mov_b64 %0, 0\n\t" WV_DPP_CHAIN7 : "=&v"(acc), "=&v"(acc2) : "v"(w), WV_G7);
+    else asm("v_mov_b64 %1, 0\n\tv_mov_b64 %0, %10\n\t" WV_DPP_CHAIN7 : "=&v"(acc), "=&v"(acc2) : "v"(w), WV_G7, "v"(init));
+  }
 #endif
   return acc + acc2;
 }
+#undef WV_G7
+#undef WV_DPP_CHAIN7
+#undef WV_DPP_STEP
 
 // Hand-over of LDS data between lanes of the ONE wavefront of a workgroup: the LDS unit works through a wavefront's
 // instructions in issue order, so a read issued after a write sees it; all that is needed is that the compiler keeps the
@@ -384,6 +436,20 @@ constexpr bool wv_rows_early(int BS, int NS, int NV, int NSTEP, int LPB, int EXT
   // (<7,4,3,10,3,3> is at 256 + 256 registers as it is: the adaptive-rho instantiations keep the old order)
   return WV_ROWS_EARLY != 0 && LNK == 0 && LPB > 0 && !(EXT & 2);
 }
+// The sweep's issue slots (profiles/wv_sweep_slots.md), a mask: 1 = the accumulators' initialisations inside wv_matvec's
+// statement, 4 = the hand-overs with chosen swap operands.  The early-clobber accumulators hold a few registers longer: an
+// instantiation takes an item where it fits without scratch and without more accumulation registers than before, from the
+// compiler's resource report.
+constexpr int wv_slots(int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK) {
+  int sl = (WV_MV_INIT ? 1 : 0) | (WV_HANDOVER ? 4 : 0);
+  // (link and stacked plans: with the hand-overs <8,2,2,10,0,0,2> takes 147 accumulation registers against 144 and both
+  // <8,2,2,8,0,.,2> one or two more)
+  if (LNK > 0) sl &= 1;
+  // (<7,4,3,10,3,1,0>, the 7-wide kernel that may start warm: 206 accumulation registers against 204 with the initialisations
+  // inside)
+  if (BS == 7 && LPB == 3 && EXT == 1) sl &= 4;
+  return sl;
+}
 //
 // LNK: link slots per variable slot (WV_NL; 0 = the kernel of a link-free plan, which holds no code of theirs).  A link row
 // has no slack and two core variables, the same in-block index k of blocks t and t + 1 (a velocity limit).  It belongs to the
@@ -402,6 +468,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr bool LREG = wv_link_regs(BS);
   constexpr bool GRES = wv_gres_fits(BS, NS, NV, NSTEP, LPB, EXT);
   constexpr bool EARLY = wv_rows_early(BS, NS, NV, NSTEP, LPB, EXT, LNK);
+  constexpr int SL = wv_slots(BS, NS, NV, NSTEP, LPB, EXT, LNK);
   constexpr int HS = (NSTEP + 1) / 2, H2 = NSTEP - HS;
   const int g = blockIdx.x, lane = threadIdx.x;
   const int b = a.list ? a.list[g + a.b0] : g + a.b0;
@@ -811,7 +878,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         const WvRow<BS> g = gq[st % PD]; const double rr = rq[st % PD], ee = eq[st % PD];
         fetch_fwd(st + PD, gq[st % PD], rq[st % PD], eq[st % PD]);
         const double w = __builtin_fma(-ee, vprev, rr);
-        vprev = wv_matvec<BS>(0.0, w, g);
+        vprev = wv_matvec<BS, true, (SL & 1) != 0>(0.0, w, g);
         vs[st] = vprev;
         if (st >= K0) gk[st - K0] = g;
       }
@@ -821,17 +888,11 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     // the middle block needs the last vector of BOTH chains: DPP row 0 holds chain A's, row 1 chain B's.  One
     // v_permlane16_swap per register half hands each row the other's (through LDS the exchange was a store, a wait and a
     // read: ~250 cycles of the ~3000 of a sweep).  All lanes take part in the swap; only the sweep lanes use the result.
-    double vother;
-    {
-      const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(vlast), (unsigned)__double2loint(vlast), false, false);
-      const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(vlast), (unsigned)__double2hiint(vlast), false, false);
-      // .x: odd rows now hold the even rows' values; .y: even rows now hold the odd rows' values
-      vother = chain ? __hiloint2double((int)hi.x, (int)lo.x) : __hiloint2double((int)hi.y, (int)lo.y);
-    }
+    double vA, vB;
+    wv_meet<(SL & 4) != 0>(vlast, chain, vA, vB);
     if (sw_store) {
       // (slot NSTEP % PD of the ring holds the middle block: fetched PD steps before the end of the forward sweep)
       const WvRow<BS> gm = gq[NSTEP % PD]; const double rm = rq[NSTEP % PD], em_ = eq[NSTEP % PD];
-      const double vA = chain ? vother : vlast, vB = chain ? vlast : vother;
       // backward sweep: block st of the chain and its coupling towards the middle, again PD steps ahead
       WvRow<BS> gb[PD]; double eb[PD];
       auto fetch_bwd = [&](int st, WvRow<BS> &g, double &e) {
@@ -841,7 +902,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       for (int i = 0; i < PD; i++) fetch_bwd(NSTEP - 1 - i, gb[i], eb[i]);
       double w = __builtin_fma(-em_, vA, rm);
       w = __builtin_fma(-emk, vB, w);
-      double xn = wv_matvec<BS>(0.0, w, gm);
+      double xn = wv_matvec<BS, true, (SL & 1) != 0>(0.0, w, gm);
       const double xmid = xn;
 #pragma unroll
       for (int st = NSTEP - 1; st >= 0; st--) {
@@ -849,7 +910,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         const WvRow<BS> g = st >= K0 ? gk[st - K0] : gb[slot]; const double ee = eb[slot];
         fetch_bwd(st - PD, gb[slot], eb[slot]);
         const double u = -(ee * xn);
-        xn = wv_matvec<BS>(vs[st], u, g);
+        xn = wv_matvec<BS, false, (SL & 1) != 0>(vs[st], u, g);
         vs[st] = xn;
       }
 #pragma unroll
@@ -883,49 +944,49 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
 #pragma unroll
     for (int i = 0; i < NSTEP; i++) {
       if (i == HS) {
-        // .x: every lane holds the value of its lane in the LOWER half; rows 0 and 1 start again from 0
-        const wv_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(vprev), (unsigned)__double2loint(vprev), false, false);
-        const wv_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(vprev), (unsigned)__double2hiint(vprev), false, false);
-        vprev = half ? __hiloint2double((int)hi.x, (int)lo.x) : 0.0;
+        // rows 2 and 3 take over the vector of their lanes in the LOWER half; rows 0 and 1 start again from 0.  The first
+        // operand of the swap is that 0: its upper half receives the vector, its lower half stays.  (vprev itself is dead:
+        // both row pairs write vs[] again in the second half.)
+        double sx = (SL & 4) ? 0.0 : vprev, sy = vprev;
+        wv_swap<32>(sx, sy);
+        vprev = (SL & 4) ? sx : (half ? sx : 0.0);
       }
       const int s = i < HS ? i : i - HS;
       const double rr = rq[i % PD], ee = eq[i % PD];
       fetch_fwd(i + PD, rq[i % PD], eq[i % PD]);
       const double w = __builtin_fma(-ee, vprev, rr);
-      vprev = wv_matvec<BS>(0.0, w, gr[s]);
+      vprev = wv_matvec<BS, true, (SL & 1) != 0>(0.0, w, gr[s]);
       vs[s] = vprev;
     }
     const double emk = lds[oEM + k8], vlast = vprev;
     // the middle block needs the last vector of both chains: row 2 holds chain A's, row 3 chain B's
-    double vother;
-    {
-      const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(vlast), (unsigned)__double2loint(vlast), false, false);
-      const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(vlast), (unsigned)__double2hiint(vlast), false, false);
-      // .x: odd rows now hold the even rows' values; .y: even rows now hold the odd rows' values
-      vother = chain ? __hiloint2double((int)hi.x, (int)lo.x) : __hiloint2double((int)hi.y, (int)lo.y);
-    }
+    double vA, vB;
+    wv_meet<(SL & 4) != 0>(vlast, chain, vA, vB);
     // (slot NSTEP % PD of the ring holds the middle block's right-hand side and coupling)
     const double rm = rq[NSTEP % PD], em_ = eq[NSTEP % PD];
-    const double vA = chain ? vother : vlast, vB = chain ? vlast : vother;
 #pragma unroll
     for (int j = 0; j < PD; j++) fetch_bwd(j, eb[j]);
     double w = __builtin_fma(-em_, vA, rm);
     w = __builtin_fma(-emk, vB, w);
-    double xn = wv_matvec<BS>(0.0, w, gmd);
-    const double xmid = xn;
+    double xn = wv_matvec<BS, true, (SL & 1) != 0>(0.0, w, gmd);
+    double xmid = xn;
 #pragma unroll
     for (int j = 0; j < NSTEP; j++) {
       if (j == H2) {
-        // .y: every lane holds the value of its lane in the UPPER half; rows 2 and 3 start again from the middle block
-        const wv_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(xn), (unsigned)__double2loint(xn), false, false);
-        const wv_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(xn), (unsigned)__double2hiint(xn), false, false);
-        xn = half ? xmid : __hiloint2double((int)hi.y, (int)lo.y);
+        // rows 0 and 1 take over the vector of their lanes in the UPPER half; rows 2 and 3 start again from the middle
+        // block.  The second operand of the swap is the middle block's x~: its lower half receives the vector, its upper
+        // half stays -- and is still the middle block's x~ for the store of row 2 below.  (xn itself is dead: both row pairs
+        // write xs[] again in the second half.)
+        double sx = xn, sy = (SL & 4) ? xmid : xn;
+        wv_swap<32>(sx, sy);
+        xn = (SL & 4) ? sy : (half ? xmid : sy);
+        if (SL & 4) xmid = sy;
       }
       const int s = bslot(j);
       const double ee = eb[j % PD];
       fetch_bwd(j + PD, eb[j % PD]);
       const double u = -(ee * xn);
-      xn = wv_matvec<BS>(vs[s], u, gr[s]);
+      xn = wv_matvec<BS, false, (SL & 1) != 0>(vs[s], u, gr[s]);
       xs[s] = xn;
     }
     if (sw_store) {
