@@ -519,6 +519,16 @@ int sco_debug_sqp_check_program(const sco_trajopt_desc *desc, int n_circle_rows,
 int sco_debug_qp_launch_plan(const int *in, const double *tol, int *out);
 int sco_debug_plan_tiers(int *mask);
 
+/* The cross-lane primitives of the kernels (csrc/sco_lanes.h) on one wavefront of `device` (diagnostics; needs a GPU).
+ * a, b, out_a, out_b: 64 doubles each, one per lane; b and out_b may be null for an op of one operand (b then reads as
+ * zeros).  op: 0 .. 7 the mover alone -- quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror, row_shr:1
+ * (no source: 0), row_shr:8 (no source: own value), row_bcast15 on row mask 0xa (0), row_bcast31 on row mask 0xc (own
+ * value); 8 broadcast of lane 23; 9 / 10 the 16- / 32-lane swap of a and b (both returned); 11 .. 14 the fold: 16 sum,
+ * 16 max, 32 sum, 32 max; 15 one scan step row_shr:2 sum, 16 one scan step row_shr:4 max; 17 / 18 row scan sum / max
+ * (lane 15 of every row); 19 / 20 wavefront scan sum / max (lane 63); 21 pair sum, 22 quad sum; 23 / 24 all-lanes sum /
+ * max; 25 / 26 shuffle sum / max; 27 out_a[l] = a[63 - l] through LDS behind the wavefront-local fence. */
+int sco_debug_lanes(int device, int op, const double *a, const double *b, double *out_a, double *out_b);
+
 /* Per-problem decision trace of the last solve, for stage-wise parity checks:
  * trace[batch][cap][8] = {kind, merit, model_merit, new_merit, trust, penalty,
  * qp_status, qp_iters}; n_entries[batch].  kind: 0 projection QP, 1 accepted step,

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libsco_hip.so")
 SOURCES = ["sco_qp.hip", "sco_admm_fast.hip", "sco_admm_reg.hip", "sco_admm_rl.hip", "sco_admm_wv.hip", "sco_qp_big.hip", "sco_sqp.hip", "sco_qp_polish.hip",
-           "qp_plan.cpp", "qp_tier.cpp", "qp_tier_choice.cpp", "qp_debug.cpp", "rl_plan.cpp", "wv_plan.cpp", "big_plan.cpp", "reg_fast_plan.cpp",
+           "sco_lanes_probe.hip", "qp_plan.cpp", "qp_tier.cpp", "qp_tier_choice.cpp", "qp_debug.cpp", "rl_plan.cpp", "wv_plan.cpp", "big_plan.cpp", "reg_fast_plan.cpp",
            "sqp_sched.cpp", "sqp_layout.cpp", "qp_polish_plan.cpp"]
-HEADERS = ["sco_internal.h", "sco_admm_check.h", "qp_plan.h", "qp_tier.h", "qp_tier_plans.h",
+HEADERS = ["sco_internal.h", "sco_admm_check.h", "sco_lanes.h", "qp_plan.h", "qp_tier.h", "qp_tier_plans.h",
            "layout_qp.h", "layout_rl.h", "layout_wv.h", "layout_big.h", "layout_reg.h", "layout_fast.h",
            "sqp_sched.h", "sqp_layout.h", "sqp_rows.h", "qp_polish_plan.h", os.path.join("..", "..", "include", "sco_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

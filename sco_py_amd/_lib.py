@@ -113,6 +113,7 @@ ABI = {
     "sco_debug_sqp_check_program": (C.c_int, [C.POINTER(TrajoptDesc), C.c_int, C.c_int, _IP, _IP, C.c_int, C.c_int]),
     "sco_debug_qp_launch_plan": (C.c_int, [_IP, _DP, _IP]),
     "sco_debug_plan_tiers": (C.c_int, [_IP]),
+    "sco_debug_lanes": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP]),
     "sco_sqp_solve": (C.c_int, [C.c_void_p, C.POINTER(SqpParams), C.POINTER(QpSettings)]),
     "sco_sqp_fetch": (C.c_int, [C.c_void_p, _DP, _IP, _IP, _IP, _LP, _DP, _DP]),
     "sco_sqp_trace": (C.c_int, [C.c_void_p, C.c_int, _DP, _IP]),

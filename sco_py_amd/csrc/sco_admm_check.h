@@ -1,8 +1,9 @@
-// sco_admm_check.h -- what every ADMM kernel tier shares: the wavefront / workgroup reductions and OSQP's termination
+// sco_admm_check.h -- what every ADMM kernel tier shares: the workgroup reductions and OSQP's termination
 // test (check_termination of osqp 0.6 as restated by oracle/osqp_ref.c: convergence, the primal and dual
 // infeasibility certificates, the 10x "approximate" pass at max_iter) with the adaptive-rho estimate.
 //
-//   * reductions: wave_sum / wave_max / wave_max63 and one block_reduce, used by every tier and by sco_sqp.hip;
+//   * the workgroup reduction block_reduce / block_reduce_sm, used by every tier and by sco_sqp.hip (what happens
+//     inside a wavefront is sco_lanes.h);
 //   * OSQP's decisions on scalars (no memory access): OsqpTol, osqp_clip_dy, the bound predicates, osqp_converged,
 //     the certificates' status choice, osqp_rho_estimate / osqp_rho_must_change;
 //   * osqp_check: the decision tree and the order of its reductions for the kernels that walk rows and columns with
@@ -18,48 +19,26 @@
 // Everything here is __device__ __forceinline__: no translation unit of its own, no ABI.
 #pragma once
 #include "sco_internal.h"
+#include "sco_lanes.h"
 
 // --------------------------------------------------------------------------
 // reductions.  Fixed trees and orders: results are run-to-run deterministic.
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {     // the summation order is part of the result
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// maximum over the wavefront, valid in lane 63: DPP row shifts and row broadcasts (VALU only; the shuffle version
-// goes through the LDS permute path six dependent times per value and made the termination test's reductions cost
-// 3.7 k cycles each, profiles/r01_check_stamps.txt).  A lane without a source keeps its own value, so a NaN
-// survives exactly when every lane holds one, as with the shuffles.
-__device__ __forceinline__ double wave_max63(double v) {
-  int lo, hi, lo2, hi2;
-#define SCO_DPP_MAX(ctrl, rmask)                                                             \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(lo, lo, ctrl, rmask, 0xf, false);                        \
-  hi2 = __builtin_amdgcn_update_dpp(hi, hi, ctrl, rmask, 0xf, false);                        \
-  v = fmax(v, __hiloint2double(hi2, lo2));
-  SCO_DPP_MAX(0x111, 0xf) SCO_DPP_MAX(0x112, 0xf) SCO_DPP_MAX(0x114, 0xf) SCO_DPP_MAX(0x118, 0xf)
-  SCO_DPP_MAX(0x142, 0xa) SCO_DPP_MAX(0x143, 0xc)
-#undef SCO_DPP_MAX
-  return v;
-}
-
-// Reduce NR per-thread values over a workgroup of NWAVES wavefronts; every thread gets the result.  `red` is
-// NWAVES * NR doubles of LDS; the first barrier protects it against a previous use.  Across the wavefronts the
-// partial results combine in the order red[0], red[1], ...  DPP_MAX: maxima by wave_max63 (lane 63 publishes)
-// instead of the shuffles (lane 0); sums always go through the shuffles.
-template <int NR, bool IS_MAX, int NWAVES, bool DPP_MAX = false>
-__device__ __forceinline__ void block_reduce(double (&v)[NR], double *red) {
+// Sums of v[0 .. NS) and maxima of v[NS .. NS + NM) over a workgroup of NWAVES wavefronts; every thread gets the
+// results.  `red` is NWAVES * (NS + NM) doubles of LDS; the first barrier protects it against a previous use.  Across
+// the wavefronts the partial results combine in the order red[0], red[1], ...  DPP_MAX: maxima by wave_scan63 (lane 63
+// publishes, and NS must be 0) instead of the shuffles (lane 0); sums always go through the shuffles.
+template <int NS, int NM, int NWAVES, bool DPP_MAX = false>
+__device__ __forceinline__ void block_reduce_sm(double (&v)[NS + NM], double *red) {
+  static_assert(!DPP_MAX || NS == 0, "one lane publishes: 63 for the DPP maxima, 0 for the shuffles");
+  constexpr int NR = NS + NM;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < NR; k++) v[k] = IS_MAX ? (DPP_MAX ? wave_max63(v[k]) : wave_max(v[k])) : wave_sum(v[k]);
+  for (int k = 0; k < NS; k++) v[k] = wave_sum(v[k]);
+#pragma unroll
+  for (int k = NS; k < NR; k++) v[k] = DPP_MAX ? wave_scan63<true>(v[k]) : wave_max(v[k]);
   __syncthreads();
-  if (lane == (IS_MAX && DPP_MAX ? 63 : 0)) {
+  if (lane == (DPP_MAX ? 63 : 0)) {
 #pragma unroll
     for (int k = 0; k < NR; k++) red[wv * NR + k] = v[k];
   }
@@ -68,9 +47,17 @@ __device__ __forceinline__ void block_reduce(double (&v)[NR], double *red) {
   for (int k = 0; k < NR; k++) {
     double r = red[k];
 #pragma unroll
-    for (int w = 1; w < NWAVES; w++) r = IS_MAX ? fmax(r, red[w * NR + k]) : r + red[w * NR + k];
+    for (int w = 1; w < NWAVES; w++) {
+      const double o = red[w * NR + k];
+      r = k < NS ? r + o : fmax(r, o);
+    }
     v[k] = r;
   }
+}
+// NR values of one kind
+template <int NR, bool IS_MAX, int NWAVES, bool DPP_MAX = false>
+__device__ __forceinline__ void block_reduce(double (&v)[NR], double *red) {
+  block_reduce_sm<IS_MAX ? 0 : NR, IS_MAX ? NR : 0, NWAVES, IS_MAX && DPP_MAX>(v, red);
 }
 
 __device__ __forceinline__ double limit_scaling(double v) {

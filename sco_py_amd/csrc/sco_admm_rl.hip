@@ -84,66 +84,23 @@ struct RlArgs {
   double *stamp;     // diagnostic build only (SCO_STAMP), else unused
 };
 
-typedef unsigned int rl_uint2 __attribute__((ext_vector_type(2)));
-// Block maximum of six values with the lane-swap folds of the W reduction (fmax instead of add; fmax is idempotent, so
-// an odd value folds with itself): 17 swap / max instructions, then two row_shr scans instead of six.  After the folds
-// lane 15 of DPP row r holds  t0: v0, v2, v1, v3 (r = 0..3)  and  t1: v4 (r = 0, 1), v5 (r = 2, 3).
-__device__ __forceinline__ double rl_fmax32(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return fmax(__hiloint2double((int)hi.x, (int)lo.x), __hiloint2double((int)hi.y, (int)lo.y));
-}
-__device__ __forceinline__ double rl_fmax16(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return fmax(__hiloint2double((int)hi.x, (int)lo.x), __hiloint2double((int)hi.y, (int)lo.y));
-}
-__device__ __forceinline__ double rl_rowmax15(double v) {        // maximum of a DPP row, valid in its lane 15
-  int lo, hi, lo2, hi2;
-#define RL_ROW_MAX(ctrl)                                                                     \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xf, 0xf, false);                          \
-  hi2 = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, 0xf, false);                          \
-  v = fmax(v, __hiloint2double(hi2, lo2));
-  RL_ROW_MAX(0x111) RL_ROW_MAX(0x112) RL_ROW_MAX(0x114) RL_ROW_MAX(0x118)
-#undef RL_ROW_MAX
-  return v;
-}
-__device__ __forceinline__ double rl_sum32(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
-__device__ __forceinline__ double rl_sum16(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
-// one step of a scan inside the DPP rows: v op (v shifted right by the row_shr control), lanes without a source keep v
-#define RL_ROW_STEP_MAX(v, ctrl)                                                             \
-  { const int lo_ = __double2loint(v), hi_ = __double2hiint(v);                              \
-    v = fmax(v, __hiloint2double(__builtin_amdgcn_update_dpp(hi_, hi_, ctrl, 0xf, 0xf, false),   \
-                                 __builtin_amdgcn_update_dpp(lo_, lo_, ctrl, 0xf, 0xf, false))); }
-#define RL_ROW_STEP_ADD(v, ctrl)                                                             \
-  { const int lo_ = __double2loint(v), hi_ = __double2hiint(v);                              \
-    v += __hiloint2double(__builtin_amdgcn_update_dpp(0, hi_, ctrl, 0xf, 0xf, true),         \
-                          __builtin_amdgcn_update_dpp(0, lo_, ctrl, 0xf, 0xf, true)); }
-__device__ __forceinline__ double rl_bcast_lane(double v, int lane) {      // lane: compile-time constant
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
 // Block reduction of the termination test: maxima of v[0..5] and sums of v[6], v[7] over the workgroup, result in
 // every thread.  Inside a wavefront the lane-swap folds of the W reduction (fmax is idempotent, so an odd value folds
-// with itself; a sum folds with zero): after them lane 15 of DPP row r holds  t0: v0, v2, v1, v3 (r = 0..3),
+// with itself; a sum folds with zero), 17 swap / max instructions, then two row_shr scans of maxima instead of six:
+// after them lane 15 of DPP row r holds  t0: v0, v2, v1, v3 (r = 0..3),
 // t1: v4 (r = 0, 1), v5 (r = 2, 3),  t2: v6 (r = 0), v7 (r = 2).  Across the wavefronts: the eight partial results of
 // value k sit in red[8 k .. 8 k + 7], ONE 8-byte read per lane fetches all 64, three row_shr steps combine the eight
 // of a value in lane 8 k + 7 and v_readlane hands it to every lane.  (r02: every thread used to read all 48 partial
 // results back: 24 KB of LDS reads per wavefront, 1.5 k cycles of a 6.4 k-cycle test.)  Fixed association order.
+// (The steps on t2, mx and sm are single lane_scan_steps, which move the high half first, where row_scan15 moves the
+// low half first: sco_lanes.h, "Order of the halves".)
 __device__ __forceinline__ void lblock_max6_sum2(double (&v)[8], double *red) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const double u0 = rl_fmax32(v[0], v[1]), u1 = rl_fmax32(v[2], v[3]), u2 = rl_fmax32(v[4], v[5]), u3 = rl_sum32(v[6], v[7]);
-  const double t0 = rl_rowmax15(rl_fmax16(u0, u1)), t1 = rl_rowmax15(rl_fmax16(u2, u2));
-  double t2 = rl_sum16(u3, 0.0);
-  RL_ROW_STEP_ADD(t2, 0x111) RL_ROW_STEP_ADD(t2, 0x112) RL_ROW_STEP_ADD(t2, 0x114) RL_ROW_STEP_ADD(t2, 0x118)
+  const double u0 = lane_fold<32, true>(v[0], v[1]), u1 = lane_fold<32, true>(v[2], v[3]), u2 = lane_fold<32, true>(v[4], v[5]);
+  const double u3 = lane_fold<32>(v[6], v[7]);
+  const double t0 = row_scan15<true>(lane_fold<16, true>(u0, u1)), t1 = row_scan15<true>(lane_fold<16, true>(u2, u2));
+  double t2 = lane_fold<16>(u3, 0.0);
+  t2 = lane_scan_step<0x111, false>(t2); t2 = lane_scan_step<0x112, false>(t2); t2 = lane_scan_step<0x114, false>(t2); t2 = lane_scan_step<0x118, false>(t2);
   __syncthreads();
   if ((lane & 15) == 15) {
     const int r = lane >> 4;
@@ -152,10 +109,10 @@ __device__ __forceinline__ void lblock_max6_sum2(double (&v)[8], double *red) {
   }
   __syncthreads();
   double mx = red[lane], sm = mx;
-  RL_ROW_STEP_MAX(mx, 0x111) RL_ROW_STEP_MAX(mx, 0x112) RL_ROW_STEP_MAX(mx, 0x114)
-  RL_ROW_STEP_ADD(sm, 0x111) RL_ROW_STEP_ADD(sm, 0x112) RL_ROW_STEP_ADD(sm, 0x114)
-  v[0] = rl_bcast_lane(mx, 7); v[1] = rl_bcast_lane(mx, 15); v[2] = rl_bcast_lane(mx, 23); v[3] = rl_bcast_lane(mx, 31);
-  v[4] = rl_bcast_lane(mx, 39); v[5] = rl_bcast_lane(mx, 47); v[6] = rl_bcast_lane(sm, 55); v[7] = rl_bcast_lane(sm, 63);
+  mx = lane_scan_step<0x111, true>(mx); mx = lane_scan_step<0x112, true>(mx); mx = lane_scan_step<0x114, true>(mx);
+  sm = lane_scan_step<0x111, false>(sm); sm = lane_scan_step<0x112, false>(sm); sm = lane_scan_step<0x114, false>(sm);
+  v[0] = lane_bcast<7>(mx); v[1] = lane_bcast<15>(mx); v[2] = lane_bcast<23>(mx); v[3] = lane_bcast<31>(mx);
+  v[4] = lane_bcast<39>(mx); v[5] = lane_bcast<47>(mx); v[6] = lane_bcast<55>(sm); v[7] = lane_bcast<63>(sm);
 }
 
 __device__ __forceinline__ double lgat(const double *base, unsigned int byte_off) {
@@ -306,37 +263,10 @@ __device__ __forceinline__ double rl_dot_row_pre(int w, const dbl2 (&val)[RW / 2
 // ---- phase (3) reduction --------------------------------------------------------------
 // The 16 partial sums of a row of the W mat-vec sit in the lanes with the same (lane >> 2) & 3:
 // 4 DPP rows (lane >> 4) x 4 lanes of a quad (lane & 3).  Two rows' partial sums are folded per
-// lane-swap instruction pair (v_permlane32_swap across the wavefront halves, v_permlane16_swap across
-// the DPP rows: after swapping register a of the upper lanes with register b of the lower lanes one
-// add leaves the pair sum of a in the lower and of b in the upper lanes), the last two levels run
-// inside the quad with quad_perm moves: 27 VALU instructions for 5 rows instead of the 60 of five
-// row_shr scans.  Fixed association order.
-__device__ __forceinline__ double rl_fold32(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
-__device__ __forceinline__ double rl_fold16(double a, double b) {
-  const rl_uint2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const rl_uint2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
-// both lanes of a pair (lane ^ 1) end up with the pair's sum
-__device__ __forceinline__ double rl_pair_sum(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return v + __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, 0xb1, 0xf, 0xf, true),     // quad_perm [1,0,3,2]
-                              __builtin_amdgcn_update_dpp(0, lo, 0xb1, 0xf, 0xf, true));
-}
-// all four lanes of a quad end up with the quad's sum
-__device__ __forceinline__ double rl_quad_sum(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  v += __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, 0xb1, 0xf, 0xf, true),     // quad_perm [1,0,3,2]
-                        __builtin_amdgcn_update_dpp(0, lo, 0xb1, 0xf, 0xf, true));
-  lo = __double2loint(v); hi = __double2hiint(v);
-  v += __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, 0x4e, 0xf, 0xf, true),     // quad_perm [2,3,0,1]
-                        __builtin_amdgcn_update_dpp(0, lo, 0x4e, 0xf, 0xf, true));
-  return v;
-}
+// lane_fold (sco_lanes.h: <32> across the wavefront halves, <16> across the DPP rows: after swapping
+// register a of the upper lanes with register b of the lower lanes one add leaves the pair sum of a
+// in the lower and of b in the upper lanes), the last two levels run inside the quad (quad_sum): 27
+// VALU instructions for 5 rows instead of the 60 of five row_shr scans.  Fixed association order.
 // acc[rr] = this lane's partial sum of tile row rr.  Returns t[n]: in the lanes of DPP row h the total of
 // tile row 4 n + 2 (h & 1) + (h >> 1) (rl_tile_row below); garbage where that index is >= TR.
 #define RL_NT(TR) (((TR) + 3) / 4)
@@ -345,25 +275,17 @@ __device__ __forceinline__ void rl_reduce_rows(const double (&acc)[TR], double (
   constexpr int NU = (TR + 1) / 2;
   double u[NU];
 #pragma unroll
-  for (int m = 0; m < NU; m++) u[m] = rl_fold32(acc[2 * m], 2 * m + 1 < TR ? acc[2 * m + 1] : 0.0);
+  for (int m = 0; m < NU; m++) u[m] = lane_fold<32>(acc[2 * m], 2 * m + 1 < TR ? acc[2 * m + 1] : 0.0);
 #pragma unroll
-  for (int n = 0; n < RL_NT(TR); n++) t[n] = rl_quad_sum(rl_fold16(u[2 * n], 2 * n + 1 < NU ? u[2 * n + 1] : 0.0));
+  for (int n = 0; n < RL_NT(TR); n++) t[n] = quad_sum(lane_fold<16>(u[2 * n], 2 * n + 1 < NU ? u[2 * n + 1] : 0.0));
 }
 __device__ __forceinline__ int rl_tile_row(int n, int h) { return 4 * n + 2 * (h & 1) + (h >> 1); }
 // Aligned layout: 8 column groups = lane bits 5, 4, 0.  Three tile rows: the swap folds over bits 5 and 4 leave the
-// total (over those bits) of row 0 / 1 / 2 in the lanes with (bit 5, bit 4) = 00 / 10 / 01, one quad_perm step adds the
+// total (over those bits) of row 0 / 1 / 2 in the lanes with (bit 5, bit 4) = 00 / 10 / 01, pair_sum adds the
 // lane pair: 12 VALU instructions for 3 rows.  Fixed association order.
 __device__ __forceinline__ double rl_reduce_al(const double (&acc)[AL_TR]) {
-  double v = rl_fold16(rl_fold32(acc[0], acc[1]), rl_fold32(acc[2], 0.0));
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  v += __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, 0xb1, 0xf, 0xf, true),     // quad_perm [1,0,3,2]
-                        __builtin_amdgcn_update_dpp(0, lo, 0xb1, 0xf, 0xf, true));
-  return v;
+  return pair_sum(lane_fold<16>(lane_fold<32>(acc[0], acc[1]), lane_fold<32>(acc[2], 0.0)));
 }
-// wavefront-local hand-over through LDS (aligned / closed assignment): the LDS operations of one wavefront complete
-// in order, so no s_barrier is needed; this only keeps the compiler from moving accesses across the hand-over
-#define RL_WAVE_SYNC() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
-                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 
 // LAY: 0 = 16 column groups of the W tile (5 x 9 at 140 core variables), 1 = 8 column groups (3 x 18, cheaper reduction, six
 // of the eight wavefronts carry W), 2 = 8 column groups with the aligned closed assignment (one barrier per iteration)
@@ -620,7 +542,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
     // (1) core right-hand side
     {
       double dv = (RL_ABLATE & 1) ? 0.0 : (RL_VARIANT & 128) ? rl_dot_col_pre<CW>(wcol, pcol, co, s_tv) : rl_dot_col<CW, NS == 2>(wcol, vcol, co, s_tv);
-      if (colsplit) dv = rl_pair_sum(dv);
+      if (colsplit) dv = pair_sum(dv);
       if (cown >= 0) rvw[k * RVS] = (sigma * xcv - qc) + dv;
     }
     STAMP(0)
@@ -669,7 +591,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
     }
     STAMP(2)
     // aligned form: the totals a row gathers were stored by its own wavefront
-    if constexpr (AL) RL_WAVE_SYNC() else if (!(RL_ABLATE & 16)) __syncthreads();
+    if constexpr (AL) wave_lds_fence(); else if (!(RL_ABLATE & 16)) __syncthreads();
     STAMP(3)
     // (Y) rows, eliminated variable, updates, next t'
     {
@@ -736,7 +658,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
       // wavefront complete in order), every other hazard is covered by the two remaining barriers; the
       // termination test after a checked step reads what all wavefronts have just written
       if ((chk || !merged) && (chk || !(RL_ABLATE & 16))) __syncthreads();
-      else RL_WAVE_SYNC()
+      else wave_lds_fence();
       STAMP(5)
     }
   };
@@ -800,7 +722,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
           }
         }
         double aty_c = rl_dot_col<CW, NS == 2>(wcol, vcol, co, swy);     // whole wave: the trip count is wave-uniform
-        if (colsplit) { const double both = rl_pair_sum(aty_c); aty_c = cown >= 0 ? both : 0.0; }   // a helper lane owns no column
+        if (colsplit) { const double both = pair_sum(aty_c); aty_c = cown >= 0 ? both : 0.0; }   // a helper lane owns no column
         CSTAMP(1)
         {
           const int cix = cown >= 0 ? cown : n_c;        // the table's zero column
@@ -853,7 +775,7 @@ __global__ __launch_bounds__(LT) void qp_admm_rl_kernel(RlArgs a) {
               double nat[1] = {0.0};
               {
                 double dv = rl_dot_col<CW, NS == 2>(wcol, vcol, co, swy);
-                if (colsplit) dv = rl_pair_sum(dv);
+                if (colsplit) dv = pair_sum(dv);
                 if (cown >= 0) nat[0] = fabs(dv / Dg[RL_CVAR]);
               }
               if (eown >= 0) nat[0] = fmax(nat[0], fabs((r_ae[0] * (r_w[0] * dyp[0]) + r_ae[1] * (r_w[1] * dyp[1])) / Dg[RL_EVAR]));

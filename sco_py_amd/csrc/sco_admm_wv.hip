@@ -122,60 +122,25 @@ struct WvArgs {
   int warm, ad_interval; double ad_tol; double *rho_b; int *rflag, *smask, *nupd;
 };
 
-// Wavefront-wide max / sum in registers: two DPP quad steps, two DPP mirror steps inside a 16-lane row, then the row and
-// half swaps (v_permlane16_swap / v_permlane32_swap).  (__shfl_xor goes through ds_bpermute: an LDS round trip per step,
-// 48 of them per termination test.)  Every lane ends with the result.
-typedef unsigned int wv_u2 __attribute__((ext_vector_type(2)));
-template <int CTRL>
-__device__ __forceinline__ double wv_dpp(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true));
-}
-template <bool IS_MAX>
-__device__ __forceinline__ double wv_wred(double v) {
-  auto op = [](double a, double b) { return IS_MAX ? fmax(a, b) : a + b; };
-  v = op(v, wv_dpp<0xb1>(v));       // quad_perm [1, 0, 3, 2]
-  v = op(v, wv_dpp<0x4e>(v));       // quad_perm [2, 3, 0, 1]
-  v = op(v, wv_dpp<0x141>(v));      // row_half_mirror
-  v = op(v, wv_dpp<0x140>(v));      // row_mirror
-  {
-    const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
-    const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
-    v = op(__hiloint2double((int)hi.x, (int)lo.x), __hiloint2double((int)hi.y, (int)lo.y));
-  }
-  {
-    const wv_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
-    const wv_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
-    v = op(__hiloint2double((int)hi.x, (int)lo.x), __hiloint2double((int)hi.y, (int)lo.y));
-  }
-  return v;
-}
-__device__ __forceinline__ double wv_wmax(double v) { return wv_wred<true>(v); }
-__device__ __forceinline__ double wv_wsum(double v) { return wv_wred<false>(v); }
-// Both register halves of two doubles through v_permlane16_swap (W = 16: the odd DPP rows of a change places with the even
-// rows of b, row 1 with row 0 and row 3 with row 2) or v_permlane32_swap (W = 32: the upper 32 lanes of a with the lower 32
-// of b).  The hand-overs of the sweeps (WV_HANDOVER) pick a and b so that the swapped registers ARE what the next step needs:
-// a copy of both halves in front of each swap, two selects per half behind it and the wait states between were 29 issue
-// slots of the 7-wide iteration.
-template <int W>
-__device__ __forceinline__ void wv_swap(double &a, double &b) {
-  const unsigned al = (unsigned)__double2loint(a), ah = (unsigned)__double2hiint(a), bl = (unsigned)__double2loint(b), bh = (unsigned)__double2hiint(b);
-  const wv_u2 lo = W == 16 ? __builtin_amdgcn_permlane16_swap(al, bl, false, false) : __builtin_amdgcn_permlane32_swap(al, bl, false, false);
-  const wv_u2 hi = W == 16 ? __builtin_amdgcn_permlane16_swap(ah, bh, false, false) : __builtin_amdgcn_permlane32_swap(ah, bh, false, false);
-  a = __hiloint2double((int)hi.x, (int)lo.x); b = __hiloint2double((int)hi.y, (int)lo.y);
-}
+// Wavefront-wide max / sum in registers, every lane ends with the result: wave_reduce_all of sco_lanes.h.
+__device__ __forceinline__ double wv_wmax(double v) { return wave_reduce_all<true>(v); }
+__device__ __forceinline__ double wv_wsum(double v) { return wave_reduce_all<false>(v); }
+// The hand-overs of the sweeps (WV_HANDOVER) pick the a and b of lane_swap so that the swapped registers ARE what the next
+// step needs: a copy of both halves in front of each swap, two selects per half behind it and the wait states between were
+// 29 issue slots of the 7-wide iteration.
 // The two chains meet: a = b = the last forward vector of the lane's chain (even rows chain A, odd rows chain B).  Behind
 // the swap a holds chain A's vector on EVERY row (the even rows kept their own, the odd rows got the even rows') and b chain
-// B's: the operands of the middle block as they are.  (Before: vother = chain ? a : b, then vA = chain ? vother : vlast and
-// vB = chain ? vlast : vother -- four selects per register half that pick, on every row, exactly these two registers.)
+// B's: the operands of the middle block as they are.  (Before, and still without DIRECT: vother = chain ? a : b, then
+// vA = chain ? vother : vlast and vB = chain ? vlast : vother -- four selects per register half that pick, on every row,
+// exactly these two registers.)
 template <bool DIRECT>
 __device__ __forceinline__ void wv_meet(double vlast, int chain, double &vA, double &vB) {
   if (DIRECT) {
     vA = vlast; vB = vlast;
-    wv_swap<16>(vA, vB);
+    lane_swap<16>(vA, vB);
   } else {
-    const wv_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(vlast), (unsigned)__double2loint(vlast), false, false);
-    const wv_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(vlast), (unsigned)__double2hiint(vlast), false, false);
+    lane_u2 lo, hi;
+    lane_swap_halves<16>(vlast, vlast, lo, hi);
     // .x: odd rows now hold the even rows' values; .y: even rows now hold the odd rows' values
     const double vother = chain ? __hiloint2double((int)hi.x, (int)lo.x) : __hiloint2double((int)hi.y, (int)lo.y);
     vA = chain ? vother : vlast; vB = chain ? vlast : vother;
@@ -376,7 +341,8 @@ __device__ __forceinline__ double wv_matvec(double init, double w, const WvRow<B
 // Hand-over of LDS data between lanes of the ONE wavefront of a workgroup: the LDS unit works through a wavefront's
 // instructions in issue order, so a read issued after a write sees it; all that is needed is that the compiler keeps the
 // program order (a wavefront-scope fence emits no instruction).  __syncthreads() would add s_waitcnt lgkmcnt(0) + s_barrier
-// four times per iteration.
+// four times per iteration.  (wave_lds_fence of sco_lanes.h is the same hand-over with a release / acquire pair of fences; this
+// kernel's code is scheduled around the single fence, so it keeps its own.)
 #define WV_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 // opaque copy of a pointer: loads through it cannot be hoisted out of the iteration loop (the constants of the termination
@@ -948,7 +914,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         // operand of the swap is that 0: its upper half receives the vector, its lower half stays.  (vprev itself is dead:
         // both row pairs write vs[] again in the second half.)
         double sx = (SL & 4) ? 0.0 : vprev, sy = vprev;
-        wv_swap<32>(sx, sy);
+        lane_swap<32>(sx, sy);
         vprev = (SL & 4) ? sx : (half ? sx : 0.0);
       }
       const int s = i < HS ? i : i - HS;
@@ -978,7 +944,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
         // half stays -- and is still the middle block's x~ for the store of row 2 below.  (xn itself is dead: both row pairs
         // write xs[] again in the second half.)
         double sx = xn, sy = (SL & 4) ? xmid : xn;
-        wv_swap<32>(sx, sy);
+        lane_swap<32>(sx, sy);
         xn = (SL & 4) ? sy : (half ? xmid : sy);
         if (SL & 4) xmid = sy;
       }

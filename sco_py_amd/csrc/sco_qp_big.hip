@@ -693,23 +693,6 @@ __global__ __launch_bounds__(256) void qp_bt_factor_kernel(BigArgs a) {
 }
 
 // ---- ADMM ---------------------------------------------------------------------------
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double bt_row16_sum(double v) {     // total of a 16-lane DPP row, valid in its lane 15
-  int lo, hi, lo2, hi2;
-#define BT_DPP_STEP(ctrl)                                                                    \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(0, lo, ctrl, 0xf, 0xf, true);                            \
-  hi2 = __builtin_amdgcn_update_dpp(0, hi, ctrl, 0xf, 0xf, true);                            \
-  v += __hiloint2double(hi2, lo2);
-  BT_DPP_STEP(0x111) BT_DPP_STEP(0x112) BT_DPP_STEP(0x114) BT_DPP_STEP(0x118)
-#undef BT_DPP_STEP
-  return v;
-}
-
 // per-problem pointers of the structured kernel
 struct BtPtrs {
   const double *As, *rho, *ls, *us, *kinv, *qs;
@@ -756,47 +739,21 @@ __device__ __forceinline__ double bt_row_step_v(const BtRow &r, double alpha, do
 }
 __device__ __forceinline__ void bt_row_zy(BtRow &r, double v) { r.z = fmin(fmax(v, r.l), r.u); r.y = r.rh * (v - r.z); }
 
-// sum over the wavefront, valid in lane 63; fixed association order (16-lane rows by
-// row_shr 1,2,4,8, then row_bcast15 into rows 1 and 3, then row_bcast31 into rows 2 and 3)
-__device__ __forceinline__ double bt_wave_sum63(double v) {
-  int lo, hi, lo2, hi2;
-#define BT_DPP_STEP(ctrl, rmask)                                                             \
-  lo = __double2loint(v); hi = __double2hiint(v);                                            \
-  lo2 = __builtin_amdgcn_update_dpp(0, lo, ctrl, rmask, 0xf, true);                          \
-  hi2 = __builtin_amdgcn_update_dpp(0, hi, ctrl, rmask, 0xf, true);                          \
-  v += __hiloint2double(hi2, lo2);
-  BT_DPP_STEP(0x111, 0xf) BT_DPP_STEP(0x112, 0xf) BT_DPP_STEP(0x114, 0xf) BT_DPP_STEP(0x118, 0xf)
-  BT_DPP_STEP(0x142, 0xa) BT_DPP_STEP(0x143, 0xc)
-#undef BT_DPP_STEP
-  return v;
-}
-
-// Column totals of NC per-lane values over the wavefront with the gfx950 lane-swap instructions:
-// v_permlane32_swap folds the two 32-lane halves of two columns into one register, v_permlane16_swap
-// folds the 16-lane rows of two such registers, and a row_shr scan finishes inside the rows: 63
-// instructions for 12 columns instead of 12 full wavefront reductions.  Fixed association order.
-typedef unsigned int bt_uint2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double bt_fold32(double a, double b) {
-  const bt_uint2 lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const bt_uint2 hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
-__device__ __forceinline__ double bt_fold16(double a, double b) {
-  const bt_uint2 lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const bt_uint2 hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
-}
+// Column totals of NC per-lane values over the wavefront with the folds of sco_lanes.h: lane_fold<32> folds
+// the two 32-lane halves of two columns into one register, lane_fold<16> folds the 16-lane rows of two
+// such registers, and a row_shr scan finishes inside the rows: 63 instructions for 12 columns instead
+// of 12 full wavefront reductions.  Fixed association order.
 // v[k] = value of column k in this lane (0 for idle lanes / unused columns); dst[k] <- sum over the wavefront
 template <int NC>
 __device__ __forceinline__ void bt_reduce_cols(const double (&v)[NC], double *dst, int ncols, int lane) {
   static_assert(NC % 4 == 0, "columns are processed four at a time");
   double u[NC / 2], t[NC / 4];
 #pragma unroll
-  for (int m = 0; m < NC / 2; m++) u[m] = bt_fold32(v[2 * m], v[2 * m + 1]);     // halves: column 2m | 2m+1
+  for (int m = 0; m < NC / 2; m++) u[m] = lane_fold<32>(v[2 * m], v[2 * m + 1]);     // halves: column 2m | 2m+1
 #pragma unroll
-  for (int n = 0; n < NC / 4; n++) t[n] = bt_fold16(u[2 * n], u[2 * n + 1]);     // rows: columns 4n, 4n+2, 4n+1, 4n+3
+  for (int n = 0; n < NC / 4; n++) t[n] = lane_fold<16>(u[2 * n], u[2 * n + 1]);     // rows: columns 4n, 4n+2, 4n+1, 4n+3
 #pragma unroll
-  for (int n = 0; n < NC / 4; n++) t[n] = bt_row16_sum(t[n]);                    // lane 15 of every row: the total
+  for (int n = 0; n < NC / 4; n++) t[n] = row_scan15<false>(t[n]);                   // lane 15 of every row: the total
   if ((lane & 15) == 15) {
     const int row = lane >> 4;
     const int off = row == 0 ? 0 : row == 1 ? 2 : row == 2 ? 1 : 3;
@@ -1204,7 +1161,7 @@ __global__ __launch_bounds__(BTT) void qp_admm_bt_kernel(BigArgs a) {
       if (dsc[0] != 0) continue;
       for (int k = 0; k < dsc[2]; k++) {
         const double v = lane < dsc[1] ? As[dsc[5] + k * dsc[6] + lane] * tp[dsc[3] + lane] : 0.0;
-        const double tot = bt_wave_sum63(v);
+        const double tot = wave_scan63<false>(v);
         if (lane == 63) s_part[dsc[14] + k] = tot;
       }
     }
@@ -1254,7 +1211,7 @@ __global__ __launch_bounds__(BTT) void qp_admm_bt_kernel(BigArgs a) {
           for (int k = 0; k < 8; k++) pv[u][k] = (16 * k < ln[u]) ? pv[u][k] : 0.0;
           double v = ((pv[u][0] + pv[u][1]) + (pv[u][2] + pv[u][3])) + ((pv[u][4] + pv[u][5]) + (pv[u][6] + pv[u][7]));
           for (int k = 128; k < ln[u]; k += 16) v += prod[pp[u] + k];
-          v = bt_row16_sum(v);
+          v = row_scan15<false>(v);
           if ((tid & 15) == 15 && c4 + u < n_c) s_r[c4 + u] = (sigma * s_x[c4 + u] - s_q[c4 + u]) + v;
         }
       }

@@ -41,8 +41,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define NWAVE (SCO_BLOCK / 64)
-
 enum { ST_PROJECT = 0, ST_CONVEXIFY = 1, ST_TRIAL = 2, ST_DONE = 3 };
 enum { STEP_PROJECT = 0, STEP_ACCEPT = 1, STEP_SHRINK = 2, STEP_YCONV = 3, STEP_XCONV = 4, STEP_BAD = 5, STEP_GROUP = 6 };
 
@@ -172,33 +170,6 @@ struct sco_sqp {
 // --------------------------------------------------------------------------
 // device helpers
 // --------------------------------------------------------------------------
-// sums v[0..NS) and maxes v[NS..NS+NM) over the workgroup; result in every thread
-template <int NS, int NM>
-__device__ __forceinline__ void block_reduce_sm(double (&v)[NS + NM], double *red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NS; k++) v[k] = wave_sum(v[k]);
-#pragma unroll
-  for (int k = NS; k < NS + NM; k++) v[k] = wave_max(v[k]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NS + NM; k++) red[wv * (NS + NM) + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NS + NM; k++) {
-    double r = red[k];
-#pragma unroll
-    for (int w = 1; w < NWAVE; w++) {
-      const double o = red[w * (NS + NM) + k];
-      r = (k < NS) ? r + o : fmax(r, o);
-    }
-    v[k] = r;
-  }
-}
-
-
 // index of the stored point whose rounded key equals that of x (d coordinates), or -1
 __device__ __forceinline__ int memo_find(const double *keys, int count, int d, const double *x) {
   for (int h = 0; h < count; h++) {
@@ -473,11 +444,6 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_proj_post_kernel(SqpDev s, QpDe
 #define WIDE_LD 33
 #define WIDE_WAVE_LDS (SCO_STATE_MAX * WIDE_LD + 2 * SCO_STATE_MAX)     // doubles per wavefront: the matrix, x'H, g
 #define WIDE_LDS_BYTES (NWAVE * WIDE_WAVE_LDS * sizeof(double))
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ void obj_shift_model_wide(double *oH, double *oA, double *ob, const double *of0, const double *x, int d, int n,
                                      int NO, int tid) {
   extern __shared__ double wide_lds[];
@@ -487,7 +453,7 @@ __device__ void obj_shift_model_wide(double *oH, double *oA, double *ob, const d
     double *Ht = oH + (size_t)t * n * n;
     const double *th = x + t * d;
     for (int e = lane; e < n * n; e += 64) A[(e / n) * WIDE_LD + e % n] = Ht[e];
-    wave_lds_sync();
+    wave_lds_fence();
     for (int sweep = 0; sweep < 12; sweep++)
       for (int p = 0; p < n - 1; p++)
         for (int q = p + 1; q < n; q++) {
@@ -501,12 +467,12 @@ __device__ void obj_shift_model_wide(double *oH, double *oA, double *ob, const d
             const double rp = A[lane * WIDE_LD + p], rq = A[lane * WIDE_LD + q];
             A[lane * WIDE_LD + p] = c * rp - sn * rq; A[lane * WIDE_LD + q] = sn * rp + c * rq;
           }
-          wave_lds_sync();
+          wave_lds_fence();
           if (lane < n) {                                   // rows p, q
             const double rp = A[p * WIDE_LD + lane], rq = A[q * WIDE_LD + lane];
             A[p * WIDE_LD + lane] = c * rp - sn * rq; A[q * WIDE_LD + lane] = sn * rp + c * rq;
           }
-          wave_lds_sync();
+          wave_lds_fence();
         }
     double lam = A[0];
     for (int i = 1; i < n; i++) lam = fmin(lam, A[i * WIDE_LD + i]);
@@ -518,13 +484,13 @@ __device__ void obj_shift_model_wide(double *oH, double *oA, double *ob, const d
       xh[lane] = acc; gl[lane] = g;
       oA[t * n + lane] = g - acc;
     }
-    wave_lds_sync();
+    wave_lds_fence();
     if (lane == 0) {
       double xHx = 0.0, gx = 0.0;
       for (int j = 0; j < n; j++) { xHx += xh[j] * th[j]; gx += gl[j] * th[j]; }
       ob[t] = (0.5 * xHx - gx) + of0[t];
     }
-    wave_lds_sync();                                        // the next term overwrites A, x'H and g
+    wave_lds_fence();                                       // the next term overwrites A, x'H and g
   }
 }
 
@@ -745,7 +711,7 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
       const RowRef q = row_ref(e, L);
       v[1] += row_viol(q, gs[e] - row_rhs(rc, q));
     }
-    block_reduce_sm<2, 0>(v, red);
+    block_reduce_sm<2, 0, NWAVE>(v, red);
     if (s.G > 0) {
       // per-group violation at the saved point
       group_sums(s, L, [&](int e, const RowRef &q) { return row_viol(q, gs[e] - row_rhs(rc, q)); },
@@ -850,7 +816,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_post_kernel(SqpDev s, QpDev q1,
   }
   __syncthreads();
   if (p.memo) memo_commit(s, sc, hkey, hn, H, xq, ev_hit);
-  block_reduce_sm<5, 1>(v, red);
+  block_reduce_sm<5, 1, NWAVE>(v, red);
   // constraint groups: which violated groups stopped improving, and do their overlapping groups too
   // (solver.py:155-161, 209-235)
   __shared__ unsigned int g_stalled, g_report;
@@ -944,7 +910,7 @@ __global__ __launch_bounds__(SCO_BLOCK) void sqp_final_kernel(SqpDev s, double *
     const double g = row_viol(q, row_value(rc, q, x + q.t * d, -1, 0.0) - row_rhs(rc, q));
     v[1] += g; v[2] = fmax(v[2], g);
   }
-  block_reduce_sm<2, 1>(v, red);
+  block_reduce_sm<2, 1, NWAVE>(v, red);
   if (tid == 0) { merit_out[b] = v[0] + s.sc[b].penalty * v[1]; viol_out[b] = v[2]; }
 }
 
