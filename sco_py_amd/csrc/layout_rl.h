@@ -1,6 +1,7 @@
 // layout_rl.h -- what rl_plan_build (rl_plan.cpp) and qp_admm_rl_kernel (sco_admm_rl.hip) must agree on: workgroup and
 // W tiling, caps, slot widths of the packed offsets, the rows of the role table.  No HIP header.
 #pragma once
+#include "layout_qp.h"
 
 #define LT 512
 #define LWV (LT / 64)
@@ -28,6 +29,17 @@
 #define ROLE_RBASE(q) ((q) < 2 ? 9 + (q) : 22)
 #define ROLE_RWID(q) ((q) < 2 ? 14 + (q) : 23)
 #define ROLE_POS(q) ((q) < 2 ? 16 + (q) : 24)
+
+// The instantiations of qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY> that exist (each with its ADAPT twin): what rl_launch
+// dispatches on and what rl_plan_build may accept -- a plan outside this list is refused, so that the tier choice goes on to
+// the next tier.  lay: 0 open assignment, 1 eight column groups (lay8), 2 aligned closed assignment.
+//   NS 2, CW 12: the six W tiles <1,2> <2,4> <3,6> <4,8> <5,9> <5,10>;  NS 2, CW 16 (wide): <5,9> <5,10>;
+//   NS 3, CW 12 or 20: <5,9> <5,10>;  lay 1 / 2: <3,18> at CW 12 or 16, NS 2.
+SCO_HD constexpr bool rl_has_kernel(int TR, int TC, int CW, int NS, int lay) {
+  return lay != 0 ? (lay == 1 || lay == 2) && NS == 2 && TR == AL_TR && TC == AL_TC && (CW == LCW || CW == LCW_MAX)
+         : TR == 5 ? (TC == 9 || TC == 10) && (NS == 2 ? CW == LCW || CW == LCW_MAX : NS == 3 && (CW == LCW || CW == LCW_MAX3))
+                   : TR >= 1 && TR <= 4 && TC == 2 * TR && NS == 2 && CW == LCW;
+}
 
 // What sco_qp_info adds to the handle's dynamic part (RlHost::lds_bytes) for the static LDS of qp_admm_rl_kernel.  NOT the
 // kernel's static LDS of today: the figure is the one reported since the kernel was written and is kept as reported.  The

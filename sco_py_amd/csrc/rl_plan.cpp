@@ -397,9 +397,10 @@ static bool rl_plan_build_ns(const QpPlan &pl, RlHost &rh, const QpCreateEnv &en
   rh.TR = std::max(1, (pl.n_c + LGI - 1) / LGI);
   rh.TC = 2 * rh.TR;
   if (rh.TR == 5 && pl.n_c <= LGJ * 9) rh.TC = 9;
-  if (rh.CW > LCW && rh.TR != 5) return false;        // the wide variants exist for the 5-row tiles only
   if (rh.NS != 2) rh.lay8 = false;
   if (rh.aligned || rh.lay8) { rh.TR = AL_TR; rh.TC = AL_TC; }
+  // the wide variants and the three-slot ones exist for the 5-row tiles only: a plan rl_launch has no kernel for is refused
+  if (!rl_has_kernel(rh.TR, rh.TC, rh.CW, rh.NS, rh.aligned ? 2 : rh.lay8 ? 1 : 0)) return false;
   return rh.lds_bytes + 40 * 1024 <= SCO_LDS_CAP;   // + 37.5 KB of static LDS
 }
 

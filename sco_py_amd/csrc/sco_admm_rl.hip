@@ -903,6 +903,7 @@ int rl_upload(const RlHost &rh, std::vector<void *> &allocs, RlDev &rd) {
 
 template <int TR, int TC, int CW, bool ADAPT, int NS = 2, int LAY = 0>
 static int rl_launch_k(const RlArgs &ra, int batch, size_t lds, hipStream_t st) {
+  static_assert(rl_has_kernel(TR, TC, CW, NS, LAY), "an instantiation rl_plan_build refuses (layout_rl.h: rl_has_kernel)");
   static bool attr_done[64] = {};
   SCO_LDS_ATTR((qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY>), 108 * 1024, attr_done);
   hipLaunchKernelGGL((qp_admm_rl_kernel<TR, TC, CW, ADAPT, NS, LAY>), dim3(batch), dim3(LT), lds, st, ra);

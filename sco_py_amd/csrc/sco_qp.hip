@@ -400,7 +400,10 @@ __device__ __forceinline__ void sweep_update(double (&t)[NT][4][4], const int (&
 }
 
 // SCO_SWEEP_NT tiles per thread (template): 1 up to order 176, 2 up to 252, 3 up to 256 (16 wavefronts leave 128
-// registers per thread, a tile takes 32)
+// registers per thread, a tile takes 32).  Reachable on chip: <1>, and <2> at orders 177 .. 194 only -- the setup kernel
+// keeps n_c (n_c + 1) / 2 doubles of S in LDS beside the pattern's values (layout_qp.h: setup_lds_doubles), so the tier choice
+// sends a core of order 195 (one box row per variable and nothing else) or more to the global-memory tier, which does not
+// come here.  <3> (orders 253 .. 256) is therefore not reachable under that LDS rule; it stays instantiated.
 template <int SCO_SWEEP_NT>
 __global__ __launch_bounds__(SCO_FACTOR_BLOCK) void qp_sweep_kernel(QpDev d) {
   const int b = d.list ? d.list[blockIdx.x + d.b0] : (int)blockIdx.x + d.b0, tid = threadIdx.x;

@@ -6,13 +6,15 @@
 // Patterns: both QPs of sqp_layout_build over trajectory descriptors (dof 1 .. 8, horizons 2 .. 24 -- past what every
 // wavefront instantiation takes --, with and without velocity limits, joint limits and the goal pin, the row families of
 // sqp_layout_sweep.cpp), wide descriptors (dof 9 .. 16: block orders 12 and 16 of the structured global-memory form, 12 x 50
-// beyond a CU's LDS), trajectory patterns with rows added that the wavefront tier refuses for a reason of its own, and
-// random sparse patterns.  Each pattern is analysed at allow_elim 0, 1 and 2, every planner runs on every analysis under
-// every combination of the switches it reads (plain struct fields of QpCreateEnv), and qp_choose_tiers runs on the pattern
-// under every combination of the planner switches and a walk through the tier switches.
+// beyond a CU's LDS; 2 x 50 with 10 obstacles: three row slots on a <4,8> tile), trajectory patterns with rows added that
+// the wavefront tier refuses for a reason of its own, and random sparse patterns.  Each pattern is analysed at allow_elim
+// 0, 1 and 2, every planner runs on every analysis under every combination of the switches it reads (plain struct fields
+// of QpCreateEnv), and qp_choose_tiers runs on the pattern under every combination of the planner switches and a walk
+// through the tier switches.
 // Checks on every accepted plan: every index it hands to its kernel is in range (rows < m, variables < n, value positions
 // < nnzA / nnzP, LDS positions inside the plan's own lds_bytes, Sell*::src inside the value array, chunk records
-// consistent with nchunks and npart, -1 only where the kernel takes it), its LDS request within the cap its planner promises.
+// consistent with nchunks and npart, -1 only where the kernel takes it), its LDS request within the cap its planner promises,
+// and a row-local plan names an instantiation its launcher has (layout_rl.h: rl_has_kernel).
 // Output: one digest line per pattern and analysis over every field and array of every plan (refused plans included:
 // the fields filled so far), one per pattern for the tier choice (return code, mask, error text) -- written to the file
 // named on the command line; the counts per planner and per WvWhy code on stdout.  Fails unless every planner accepts and
@@ -174,6 +176,7 @@ static const char *ck_pc(const QpPlan &pl, const std::vector<int> &ptr, const st
 static const char *ck_rl(const QpPlan &pl, const RlHost &r) {
   CK(r.lds_bytes + 40 * 1024 <= (size_t)SCO_LDS_CAP && r.NS >= 2 && r.NS <= LNS_MAX);
   CK(r.CW == LCW || r.CW == LCW_MAX || (r.NS == 3 && r.CW == LCW_MAX3));
+  CK(rl_has_kernel(r.TR, r.TC, r.CW, r.NS, r.aligned ? 2 : r.lay8 ? 1 : 0));      // rl_launch has this instantiation
   const int CP = r.CW / 2, RP = (r.CW > LCW ? LRW_MAX : LRW) / 2, slots = CP + r.NS * RP + 1, lds_el = (int)(r.lds_bytes / 8);
   CK((int)r.off.size() == slots * LT && (int)r.role.size() == RL_ROLES * LT);
   // (the images have one item per thread, or, in the compact form of the closed assignments, one per thread with entries)
@@ -419,8 +422,10 @@ int main(int argc, char **argv) {
             if (sweep_desc(desc, "traj")) return 1;
           }
   // ---- wide descriptors: block orders 12 and 16 of the structured form; 12 x 50 is beyond a CU's LDS without force_big
+  // ... and a long narrow one (2 x 50, 10 obstacles): 500 slacks beside a core of 100 leave too few threads for the free rows
+  // in two row slots, on a W tile that has no three-slot kernel (rl_plan_build refuses; the tier choice goes on)
   {
-    const int wide[][3] = {{9, 4, 2}, {12, 6, 2}, {12, 50, 8}, {13, 5, 3}, {16, 4, 2}, {16, 12, 6}};
+    const int wide[][3] = {{9, 4, 2}, {12, 6, 2}, {12, 50, 8}, {13, 5, 3}, {16, 4, 2}, {16, 12, 6}, {2, 50, 10}};
     for (const auto &w : wide)
       for (int fl = 0; fl < 4; fl += 3) {
         const sco_trajopt_desc desc = {3, w[0], w[1], 1, w[2], SCO_FAM_POINT_CIRCLES | (fl ? SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS : 0), 0, 0, 0, 0};

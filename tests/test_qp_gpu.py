@@ -463,8 +463,10 @@ def test_adaptive_rho_on_random_sparsity_patterns(gpu, monkeypatch, seed, tier):
 
 def test_both_core_inversion_routes_agree(gpu, monkeypatch):
     """W = S^-1 by register-resident Gauss-Jordan sweeps (default) and by Cholesky + triangular inverse
-    (SCO_QP_FACTOR_CHOLESKY=1): same statuses and iteration counts, answers within 1e-10; cores of order 3, 15, 60,
-    140 (one tile per thread) and 200 (two tiles per thread)."""
+    (SCO_QP_FACTOR_CHOLESKY=1): same statuses and iteration counts, answers within 1e-10; cores of order 3, 15, 60 and
+    140 (one tile per thread).  The core of order 200 is beyond a CU's LDS (the setup asks for n_c (n_c + 1) / 2 doubles on
+    top of the pattern) and goes to the structured global-memory tier, where neither route runs: the switch must change
+    nothing there.  Two tiles per thread: test_both_core_inversion_routes_agree_on_the_largest_on_chip_cores."""
     rng = np.random.default_rng(41)
     for shape in ((1, 3, 2), (5, 3, 4), (20, 3, 2), (20, 7, 10), (25, 8, 3)):
         probs = [penalty_qp(rng, *shape) for _ in range(2)]
@@ -474,6 +476,29 @@ def test_both_core_inversion_routes_agree(gpu, monkeypatch):
         monkeypatch.setenv("SCO_QP_FACTOR_CHOLESKY", "1")
         _, x_c, st_c, it_c = _check(probs, check=[])
         assert np.array_equal(st_s, st_c) and np.array_equal(it_s, it_c) and np.abs(x_s - x_c).max() < 1e-10
+
+
+ON_CHIP_CORES = [(176, (44, 4, 1)), (177, (59, 3, 1)), (180, (45, 4, 1)), (190, (190, 1, 0)), (194, (194, 1, 0))]
+
+
+@pytest.mark.parametrize("order,shape", ON_CHIP_CORES, ids=["order %d" % n for n, _ in ON_CHIP_CORES])
+def test_both_core_inversion_routes_agree_on_the_largest_on_chip_cores(gpu, monkeypatch, order, shape):
+    """Cores that stay on chip (no bit 3 in the handle's tiers) around the step from one 4 x 4 tile per thread of
+    qp_sweep_kernel (up to order 176) to two (from 177): 176, 177, 180, 190 and 194, the largest order the tier choice keeps
+    on chip (tests/test_qp_plan.py::test_core_orders_that_stay_on_chip).  Both routes against the oracle, and against each
+    other: same statuses and iteration counts, answers within 1e-10."""
+    T, d, r = shape
+    rng = np.random.default_rng(47)
+    probs = [penalty_qp(rng, *shape) for _ in range(2)]
+    n, m, Pp, Pi, Ap, Ai, *_ = _stack(probs)
+    monkeypatch.delenv("SCO_QP_FACTOR_CHOLESKY", raising=False)
+    assert _tiers(n, m, Pp, Pi, Ap, Ai) & 8 == 0
+    info, x_s, st_s, it_s = _check(probs)
+    assert info["n_core"] == order == T * d
+    monkeypatch.setenv("SCO_QP_FACTOR_CHOLESKY", "1")
+    assert _tiers(n, m, Pp, Pi, Ap, Ai) & 8 == 0
+    _, x_c, st_c, it_c = _check(probs)
+    assert np.array_equal(st_s, st_c) and np.array_equal(it_s, it_c) and np.abs(x_s - x_c).max() < 1e-10
 
 
 def test_null_index_array_with_a_non_empty_pattern_is_rejected(gpu):

@@ -209,3 +209,29 @@ def test_which_structured_plans_form_their_blocks_on_the_matrix_cores(name, kw, 
     if want[3]:
         monkeypatch.setenv("SCO_QP_NO_MFMA", "1")
         assert lib.sco_debug_bt_plan(ip(info)) == 0 and tuple(info[:5]) == want[:3] + (0, 1)
+
+
+@pytest.mark.parametrize("shape,on_chip", [((44, 4, 1), True), ((59, 3, 1), True), ((45, 4, 1), True), ((190, 1, 0), True), ((194, 1, 0), True),
+                                           ((195, 1, 0), False), ((185, 1, 1), False), ((25, 8, 3), False)])
+def test_core_orders_that_stay_on_chip(shape, on_chip, monkeypatch):
+    """The setup kernel keeps the packed lower triangle of S, n_c (n_c + 1) / 2 doubles, in LDS beside the pattern's values
+    (layout_qp.h: setup_lds_doubles), so a core of order 195 no longer fits the 160 KB of a CU even with nothing but one box
+    row per variable: mask bit 3 (global-memory tier).  Of the register-resident Gauss-Jordan sweep (qp_sweep_kernel<NT>:
+    one 4 x 4 tile per thread up to order 176, two up to 252, three up to 256) only <1> and <2> are reachable on chip -- <2>
+    at orders 177 .. 194 --, <3> is not."""
+    for name in ("SCO_QP_FORCE_BIG", "SCO_QP_NO_ELIM", "SCO_QP_NO_RL", "SCO_QP_NO_REG", "SCO_QP_NO_FAST"):
+        monkeypatch.delenv(name, raising=False)
+    Pm, qv, Am, lv, uv = penalty_qp(np.random.default_rng(0), *shape)
+    P = sp.triu(sp.csc_matrix(Pm != 0), format="csc"); A = sp.csc_matrix(Am != 0)
+    P.sort_indices(); A.sort_indices()
+    lib = _lib.load()
+    ip = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int))
+    Pp, Pi, Ap, Ai = (np.ascontiguousarray(a, dtype=np.int32) for a in (P.indptr, P.indices, A.indptr, A.indices))
+    sizes = np.zeros(16, dtype=np.int32); mask = np.zeros(1, dtype=np.int32)
+    lib.sco_debug_plan_build.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.c_int, C.POINTER(C.c_int)]
+    assert lib.sco_debug_plan_build(len(qv), len(lv), ip(Pp), ip(Pi), ip(Ap), ip(Ai), 1, ip(sizes)) == 0
+    assert sizes[1] == shape[0] * shape[1]
+    assert lib.sco_debug_plan_tiers(ip(mask)) == 0
+    assert (mask[0] & 8 == 0) == on_chip, mask[0]
+    if not on_chip:
+        assert mask[0] == 24                           # the structured form: no dense inverse, neither inversion route
