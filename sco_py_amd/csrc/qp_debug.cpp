@@ -2,6 +2,7 @@
 // analysis, the tier plans and the tier choice for the CPU test-suite.  Plain C++, no HIP call.  Every entry point reads the
 // environment afresh (qp_create_env), so a test that sets a variable and then asks for a plan sees it.
 #include "qp_tier_plans.h"
+#include "layout_fast.h"
 #include "layout_wv.h"
 
 #include <algorithm>
@@ -31,6 +32,25 @@ extern "C" int sco_debug_rl_plan(int *info) {
   RlHost rh;
   const bool ok = rl_plan_build(g_dbg_plan, rh, qp_create_env());
   info[0] = ok ? 1 : 0; info[1] = rh.CW; info[2] = rh.TR; info[3] = rh.TC; info[4] = (int)rh.lds_bytes; info[5] = rh.merged ? 1 : 0; info[6] = rh.aligned ? 1 : rh.lay8 ? 2 : 0; info[7] = rh.NS;
+  return SCO_OK;
+}
+// Host-only: the sliced-ELL plan of that pattern (whether or not an earlier tier of the choice takes it) and the
+// instantiation fast_launch would pick.  info[0] fits, [1] TR, [2] TC, [3] capped dots (<12, 8, 12, 8>; 0: the looping form),
+// [4] rows per thread, [5] LDS bytes
+extern "C" int sco_debug_fast_plan(int *info) {
+  FastHost fh;
+  const bool ok = fast_plan_build(g_dbg_plan, fh);
+  const int nq = fast_rows_per_thread(g_dbg_plan.m);
+  info[0] = ok ? 1 : 0; info[1] = fh.TR; info[2] = fh.TC; info[3] = (fh.capped && nq == 2) ? 1 : 0; info[4] = nq; info[5] = (int)fh.lds_bytes;
+  return SCO_OK;
+}
+// Host-only: the register-offset plan of that pattern.  info[0] fits (the caps and the per-thread programs), [1] TR, [2] TC,
+// [3] CW, [4] RW, [5] PX, [6] dynamic LDS bytes (the kernel's static LDS comes on top: reg_static_lds)
+extern "C" int sco_debug_reg_plan(int *info) {
+  RegHost rh;
+  int CW = 0, RW = 0, PX = 0;
+  const bool ok = reg_caps_for(g_dbg_plan, &CW, &RW, &PX) && reg_plan_build(g_dbg_plan, CW, RW, PX, rh);
+  info[0] = ok ? 1 : 0; info[1] = rh.TR; info[2] = rh.TC; info[3] = rh.CW; info[4] = rh.RW; info[5] = rh.PX; info[6] = (int)rh.lds_bytes;
   return SCO_OK;
 }
 // Host-only: would that pattern land on the wavefront tier with the link-free plan?  info[0] fits, [1] block order,

@@ -397,8 +397,8 @@ static int launch_one(const AdmmArgs &a, const FastDev &fd, size_t lds, hipStrea
 
 template <int TR, int TC>
 static int launch_tile(const AdmmArgs &a, const FastHost &fh, const FastDev &fd, hipStream_t st) {
-  // more than 2 x 512 rows: three rows per thread (looping dots only: patterns this large have wide columns anyway)
-  if (a.d.m > 2 * FT) return launch_one<TR, TC, 0, 0, 0, 0, 3>(a, fd, fh.lds_bytes, st);
+  // more than 2 x 512 rows: three rows per thread, looping dots only (layout_fast.h)
+  if (fast_rows_per_thread(a.d.m) == 3) return launch_one<TR, TC, 0, 0, 0, 0, 3>(a, fd, fh.lds_bytes, st);
   if (fh.capped) return launch_one<TR, TC, 12, 8, 12, 8, 2>(a, fd, fh.lds_bytes, st);
   return launch_one<TR, TC, 0, 0, 0, 0, 2>(a, fd, fh.lds_bytes, st);
 }
