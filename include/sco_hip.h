@@ -256,6 +256,20 @@ void sco_sqp_default_params(sco_sqp_params *p);
 #define SCO_OP_EXP 12
 #define SCO_OP_SQUARE 13  /* a -> a * a                            */
 #define SCO_PROGRAM_STACK 16   /* deepest stack a row's program may need */
+#define SCO_FAM_ARM_SPATIAL 7   /* spatial serial arm of revolute joints, link spheres vs sphere obstacles:
+                                  g[k*O + o](theta) = r_o + rad_k - || p_k(theta) - c_o ||  <= 0,
+                                  p_k = forward kinematics in three dimensions: joint i sits at off_i in its parent's frame
+                                  and turns by theta_i about the unit axis ax_i of its own frame (Rodrigues' formula); link
+                                  point k rides on the frame of joint point_link[k], behind that joint's rotation, at pos_k.
+                                  Geometry via sco_sqp_load_spatial; of sco_sqp_load, point_link is read (the frame of every
+                                  point) and link_len / point_frac / obstacles are not.  dof <= 16, any n_points and
+                                  n_obstacles >= 1; rows, layout and kernel tiers are those of SCO_FAM_ARM_CIRCLES.  Flags:
+                                  SCO_FAM_FLAG_VEL_LIMITS, SCO_FAM_FLAG_JOINT_LIMITS, SCO_FAM_FLAG_ACC_COST; general affine
+                                  rows, objective weights and constraint groups work as for the planar arm.  Refused:
+                                  SCO_FAM_FLAG_EE_COST and the program objectives, span > 1, n_eq_rows > 0 (there is no
+                                  3-D reach equality or end-effector term, no prismatic joint and no capsule).  Jacobians by
+                                  central differences or (analytic_jac = 1) from the geometric Jacobian
+                                  d p_k / d theta_j = a_j x (p_k - o_j) */
 
 /* Structure of a batch of trajectory problems (shared by all `batch` problems):
  * variables theta[t][j], t < horizon, j < dof, flattened time-major (n_x = horizon*dof);
@@ -369,6 +383,15 @@ int sco_sqp_load_target(sco_sqp *h, const double *target);
 /* SCO_FAM_STATE_QUADRATIC only, after sco_sqp_load: Q[batch][n_obstacles][dof*dof] (symmetric), a[batch][n_obstacles][dof],
  * c[batch][n_obstacles].  With n_eq_rows > 0 the last n_eq_rows rows of every timestep are equalities g = 0 (r03). */
 int sco_sqp_load_quadratic(sco_sqp *h, const double *Q, const double *a, const double *c);
+/* SCO_FAM_ARM_SPATIAL only, after sco_sqp_load; sco_sqp_solve answers SCO_ERR_STATE until it has been called.  May be repeated:
+ * the handle keeps its buffers.  SCO_ERR_ARG for a null pointer, a non-finite number, a negative radius, an axis whose length
+ * is further than 1e-9 from 1, or a handle of another family; nothing is copied then. */
+int sco_sqp_load_spatial(sco_sqp *h,
+    const double *joint_off,   /* [batch][dof][3]          */
+    const double *joint_axis,  /* [batch][dof][3], unit    */
+    const double *point_pos,   /* [batch][n_points][3]     */
+    const double *point_rad,   /* [batch][n_points], >= 0  */
+    const double *spheres);    /* [batch][n_obstacles][4] = (cx, cy, cz, r), r >= 0 */
 /* SCO_FAM_STATE_PROGRAM only, after sco_sqp_load: row r's program is words[2 * row_ptr[r] .. 2 * row_ptr[r+1]) as (op, arg)
  * pairs, the last one SCO_OP_END; consts[n_consts]; params[batch][n_params] (n_params may be 0).  There are R = n_obstacles
  * programs (the rows of a block: inequalities first, then the n_eq_rows equalities; SCO_OP_X addresses the span * dof numbers

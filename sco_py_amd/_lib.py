@@ -88,6 +88,7 @@ ABI = {
     "sco_sqp_load": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, _IP, _DP, _DP]),
     "sco_sqp_load_target": (C.c_int, [C.c_void_p, _DP]),
     "sco_sqp_load_quadratic": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "sco_sqp_load_spatial": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, _DP]),
     "sco_sqp_load_program": (C.c_int, [C.c_void_p, C.c_int, _IP, _IP, C.c_int, _DP, C.c_int, _DP]),
     "sco_sqp_load_program_steps": (C.c_int, [C.c_void_p, C.c_int, _IP, _IP, C.c_int, _DP, C.c_int, _DP]),
     "sco_sqp_load_obj_weights": (C.c_int, [C.c_void_p, _DP]),

@@ -14,12 +14,14 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
+from .workloads import SPATIAL_KEYS
 
 SCO_FAM_ARM_CIRCLES = 1
 SCO_FAM_ARM_REACH = 2
 SCO_FAM_POINT_CIRCLES = 3
 SCO_FAM_STATE_QUADRATIC = 4
 SCO_FAM_STATE_PROGRAM = 5
+SCO_FAM_ARM_SPATIAL = 7
 SCO_FAM_FLAG_VEL_LIMITS = 16
 SCO_FAM_FLAG_JOINT_LIMITS = 32
 SCO_FAM_FLAG_EE_COST = 64
@@ -43,6 +45,11 @@ class TrajOptBatch(object):
     linear rows lo <= theta[t] <= hi, SCO_FAM_FLAG_JOINT_LIMITS; ``ee_cost=True``: a non-quadratic objective term
     weight * ||ee(theta[t]) - target||^2 per timestep, convexified to degree 2 like ``Prob.add_obj_expr`` on a plain
     ``Expr`` (numeric Hessian + eigenvalue shift), SCO_FAM_FLAG_EE_COST)
+    ``spatial=True``: SCO_FAM_ARM_SPATIAL, a spatial serial arm of revolute joints whose link spheres keep off sphere
+    obstacles (``load(..., joint_off=, joint_axis=, point_pos=, point_rad=, spheres=)``; ``point_link`` names the joint frame
+    a point rides on, ``link_len`` / ``point_frac`` / ``obstacles`` are not read; velocity limits, joint limits, the
+    acceleration term, general affine rows, objective weights and groups as for the planar arm; no reach equality and no
+    end-effector term);
     ``point=True``: SCO_FAM_POINT_CIRCLES, a point robot in the plane (state of a timestep: dof >= 2 numbers, the first
     two its position; n_points = 1; link data are not read) instead of the arm; ``quadratic=True``:
     SCO_FAM_STATE_QUADRATIC, n_obstacles rows 1/2 x' Q_r x + a_r' x + c_r <= 0 on the state of every timestep with
@@ -61,7 +68,8 @@ class TrajOptBatch(object):
 
     def __init__(self, batch, dof, horizon, n_points, n_obstacles, device=0, analytic_jac=False,
                  prox_count=2, reach=False, vel_limits=False, joint_limits=False, ee_cost=False, point=False,
-                 quadratic=False, program=False, n_eq_rows=0, lin_rows=None, circle_rows=0, acc_cost=False):
+                 quadratic=False, program=False, n_eq_rows=0, lin_rows=None, circle_rows=0, acc_cost=False,
+                 spatial=False):
         """acc_cost (r04): the quadratic objective carries an acceleration term sum_t sum_j a_j (x[t+2][j] - 2 x[t+1][j] + x[t][j])^2
         (``load(acc_weights=)``, (B, dof)); fixed at creation because P gets a second super-diagonal block.
         circle_rows (r04, program family, span 1): the first ``circle_rows`` of the ``n_obstacles`` rows of a block are keep-out
@@ -83,6 +91,9 @@ class TrajOptBatch(object):
         self.quadratic = bool(quadratic)   # SCO_FAM_STATE_QUADRATIC: n_obstacles general quadratic rows per timestep
         if (self.point or self.quadratic) and (self.reach or self.ee_cost):
             raise ValueError("the point-robot and quadratic-row families have neither the reach equality nor the objective term")
+        self.spatial = bool(spatial)       # SCO_FAM_ARM_SPATIAL: link spheres of a spatial serial arm against sphere obstacles
+        if self.spatial and (self.point or self.quadratic or bool(program) or self.reach or self.ee_cost or n_eq_rows):
+            raise ValueError("one family per batch; the spatial arm has neither the reach equality nor the objective term")
         self.program = bool(program)       # SCO_FAM_STATE_PROGRAM: rows as closed-form programs (sco_py_amd.rowexpr)
         if sum((self.point, self.quadratic, self.program)) > 1 or (self.program and (self.reach or self.ee_cost)):
             raise ValueError("one family per batch; the program family has neither the reach equality nor the arm's objective term")
@@ -103,7 +114,7 @@ class TrajOptBatch(object):
         self.n_blocks = self.T - self.span + 1
         desc = _lib.TrajoptDesc(self.B, self.d, self.T, self.K, self.O,
                                 (SCO_FAM_STATE_PROGRAM if self.program else SCO_FAM_STATE_QUADRATIC if self.quadratic else
-                                 SCO_FAM_POINT_CIRCLES if self.point else
+                                 SCO_FAM_POINT_CIRCLES if self.point else SCO_FAM_ARM_SPATIAL if self.spatial else
                                  SCO_FAM_ARM_REACH if self.reach else SCO_FAM_ARM_CIRCLES) |
                                 (SCO_FAM_FLAG_VEL_LIMITS if self.vel_limits else 0) |
                                 (SCO_FAM_FLAG_JOINT_LIMITS if self.joint_limits else 0) |
@@ -150,7 +161,8 @@ class TrajOptBatch(object):
 
     def load(self, x0, start, goal, link_len, point_link, point_frac, obstacles, target=None, vmax=None,
              jlo=None, jhi=None, cost_weight=None, cost_target=None, quad_Q=None, quad_a=None, quad_c=None,
-             row_program=None, row_params=None, obj_weights=None, lin_vals=None, lin_rhs=None, acc_weights=None):
+             row_program=None, row_params=None, obj_weights=None, lin_vals=None, lin_rhs=None, acc_weights=None,
+             joint_off=None, joint_axis=None, point_pos=None, point_rad=None, spheres=None):
         """Upload per-problem data (host arrays, copied).  ``target`` (B, 2): end-effector
         position of the reach variant (``goal`` is then ignored by the device).  r04: ``row_params`` may be (B, T, n_params) --
         one parameter vector per timestep (block t and the objective term of timestep t read row_params[b, t]);
@@ -169,6 +181,15 @@ class TrajOptBatch(object):
         _lib.check(_lib.load().sco_sqp_load(self._h, _lib.dptr(x0), _lib.dptr(start), _lib.dptr(goal),
                                             _lib.dptr(link_len), _lib.iptr(point_link), _lib.dptr(point_frac),
                                             _lib.dptr(obstacles)))
+        if self.spatial:
+            if any(a is None for a in (joint_off, joint_axis, point_pos, point_rad, spheres)):
+                raise ValueError("the spatial arm needs joint_off (B, d, 3), joint_axis (B, d, 3), point_pos (B, K, 3), point_rad (B, K) "
+                                 "and spheres (B, O, 4)")
+            jo = arr(joint_off, (B, d, 3)); ja = arr(joint_axis, (B, d, 3)); pp = arr(point_pos, (B, K, 3))
+            prd = arr(point_rad, (B, K)); sph = arr(spheres, (B, O, 4))
+            _lib.check(_lib.load().sco_sqp_load_spatial(self._h, _lib.dptr(jo), _lib.dptr(ja), _lib.dptr(pp), _lib.dptr(prd), _lib.dptr(sph)))
+        elif any(a is not None for a in (joint_off, joint_axis, point_pos, point_rad, spheres)):
+            raise ValueError("the batch was created without the spatial arm (spatial=True)")
         if self.quadratic:
             if quad_Q is None or quad_a is None or quad_c is None:
                 raise ValueError("the quadratic-row family needs quad_Q (B, O, d, d), quad_a (B, O, d), quad_c (B, O)")
@@ -322,13 +343,14 @@ def solve_batch(batch_arrays, params=None, qp_settings=None, device=0, analytic_
                       point=bool(a.get("point")), quadratic=a.get("quad_Q") is not None,
                       program=a.get("row_program") if a.get("row_program") is not None else False,
                       n_eq_rows=a.get("quad_n_eq", 0), lin_rows=a.get("lin_rows"), circle_rows=a.get("circle_rows", 0),
-                      acc_cost=a.get("acc_w") is not None) as tb:
+                      acc_cost=a.get("acc_w") is not None, spatial=bool(a.get("spatial"))) as tb:
         tb.load(a["x0"], a["start"], a["goal"], a["link_len"], a["point_link"], a["point_frac"], a["obstacles"],
                 target=a.get("target"), vmax=a.get("vmax"), jlo=a.get("jlo"), jhi=a.get("jhi"),
                 cost_weight=a.get("cost_weight"), cost_target=a.get("cost_target"),
                 quad_Q=a.get("quad_Q"), quad_a=a.get("quad_a"), quad_c=a.get("quad_c"),
                 row_program=a.get("row_program"), row_params=a.get("row_params"), obj_weights=a.get("obj_w"),
-                lin_vals=a.get("lin_vals"), lin_rhs=a.get("lin_rhs"), acc_weights=a.get("acc_w"))
+                lin_vals=a.get("lin_vals"), lin_rhs=a.get("lin_rhs"), acc_weights=a.get("acc_w"),
+                **{k: a.get(k) for k in SPATIAL_KEYS})
         if a.get("groups") is not None:
             tb.set_groups(a["groups"])
         tb.solve(params, qp_settings)

@@ -111,6 +111,8 @@ struct SqpDev {
   // problem data
   double *x0, *start, *goal, *link_len, *obstacles, *target;   // [B][...]
   const int *point_link; const double *point_frac;    // [K]
+  // SCO_FAM_ARM_SPATIAL (sco_sqp_load_spatial): joint offsets and unit axes, link points and their radii, sphere obstacles
+  double *sp_off, *sp_axis, *sp_pos, *sp_rad, *sp_sph;   // [B][d][3], [B][d][3], [B][K][3], [B][K], [B][O][4]
   // SQP state
   double *x, *x_saved, *gsave, *J, *bmod, *trace;
   unsigned char *mask;
@@ -158,7 +160,7 @@ struct sco_sqp {
   void *accw_buf = nullptr;                                    // sco_sqp_load_acc_weights
   bool gen_loaded = false;
   size_t prog_bytes[4] = {0, 0, 0, 0};
-  bool loaded = false, solved = false, target_loaded = false, vel_loaded = false, jl_loaded = false, cost_loaded = false, quad_loaded = false, prog_loaded = false;
+  bool loaded = false, solved = false, target_loaded = false, vel_loaded = false, jl_loaded = false, cost_loaded = false, quad_loaded = false, prog_loaded = false, spatial_loaded = false;
   double last_ms[5] = {0, 0, 0, 0, 0};
   int rounds = 0;          // 1 (projection) + the rounds of the group that needed most
   int launches = 0;        // round launches over all stream groups
@@ -238,7 +240,9 @@ __device__ __forceinline__ RowCtx row_ctx(const SqpDev &s, int b) {
   return RowCtx{s.link_len + (size_t)b * s.d, s.obstacles + (size_t)b * s.O * 3, s.target + (size_t)b * 2, s.point_link, s.point_frac,
                 s.ds, s.O, s.point,
                 s.qQ + (size_t)b * s.O * s.ds * s.ds, s.qa + (size_t)b * s.O * s.ds, s.qc + (size_t)b * s.O,
-                s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1};
+                s.pw, s.pptr, s.pconst, s.ppar + (size_t)b * s.n_par * (s.par_step ? s.T : 1), s.par_step, s.R1,
+                s.sp_off + (size_t)b * s.d * 3, s.sp_axis + (size_t)b * s.d * 3, s.sp_pos + (size_t)b * s.K * 3, s.sp_rad + (size_t)b * s.K,
+                s.sp_sph + (size_t)b * s.O * 4};
 }
 __device__ __forceinline__ ObjCtx obj_ctx(const SqpDev &s, int b) {
   return ObjCtx{s.cost, s.link_len + (size_t)b * s.d, s.d, s.ctgt[(size_t)b * 2], s.ctgt[(size_t)b * 2 + 1], s.cw[b]};
@@ -559,6 +563,8 @@ __device__ __forceinline__ void sqp_pre_body(SqpDev &s, QpDev &q1, SqpParamsDev 
         val = cJ[(((size_t)q.blk * HC + cv_hit[q.blk]) * RM + q.r) * ds + j];
       } else if (s.analytic_jac) {
         val = row_grad(rc, q, th, j);
+      } else if (row_ignores(rc, q, j)) {
+        val = 0.0;                               // (the central differences of a row that does not see coordinate j: 0 on the host too)
       } else {
         val = central_diff(th[j], j, [&](int jj, double h) { return row_value(rc, q, th, jj, h); });
       }
@@ -1013,6 +1019,11 @@ static int sqp_create_impl(sco_sqp *h, int device, const SqpLayout &L) {
     const bool quadf = L.point == ROWS_QUADRATIC;
     AL(qQ, quadf ? (size_t)B * O * ds * ds : 1) AL(qa, quadf ? (size_t)B * O * ds : 1) AL(qc, quadf ? (size_t)B * O : 1)
   }
+  {
+    const bool spf = L.point == ROWS_SPATIAL;
+    AL(sp_off, spf ? (size_t)B * d * 3 : 1) AL(sp_axis, spf ? (size_t)B * d * 3 : 1) AL(sp_pos, spf ? (size_t)B * K * 3 : 1)
+    AL(sp_rad, spf ? (size_t)B * K : 1) AL(sp_sph, spf ? (size_t)B * O * 4 : 1)
+  }
   AL(x, (size_t)B * n_x) AL(x_saved, (size_t)B * n_x) AL(gsave, (size_t)B * m_nl) AL(J, (size_t)B * m_nl * ds)
   AL(bmod, (size_t)B * m_nl) AL(trace, (size_t)B * s.trace_cap * TRACE_W) AL(mask, (size_t)B * m_nl * ds)
   AL(sc, (size_t)B) AL(active, (size_t)B) AL(n_active, SQP_MAX_GROUPS) AL(newqp, (size_t)B) AL(list_buf, (size_t)B)
@@ -1170,6 +1181,36 @@ extern "C" int sco_sqp_load_quadratic(sco_sqp *h, const double *Q, const double 
   SCO_HIP(hipMemcpyAsync(h->d.qc, c, B * O * sizeof(double), hipMemcpyHostToDevice, h->stream));
   SCO_HIP(hipStreamSynchronize(h->stream));
   h->quad_loaded = true; h->solved = false;
+  return SCO_OK;
+}
+
+// SCO_FAM_ARM_SPATIAL: the arm's geometry and the sphere obstacles of every problem, into buffers the handle owns since its
+// creation (the call may be repeated).  Everything is checked before anything is copied.
+extern "C" int sco_sqp_load_spatial(sco_sqp *h, const double *joint_off, const double *joint_axis, const double *point_pos,
+                                    const double *point_rad, const double *spheres) {
+  if (!h || !joint_off || !joint_axis || !point_pos || !point_rad || !spheres) { sco_set_error("sco_sqp_load_spatial: null pointer"); return SCO_ERR_ARG; }
+  if ((h->desc.family & 15) != SCO_FAM_ARM_SPATIAL) { sco_set_error("sco_sqp_load_spatial: family has no spatial arm"); return SCO_ERR_ARG; }
+  if (!h->loaded) { sco_set_error("sco_sqp_load_spatial: call sco_sqp_load first"); return SCO_ERR_STATE; }
+  const SqpDev &s = h->d;
+  const size_t B = s.batch, d = s.d, K = s.K, O = s.O;
+  const double *arr[5] = {joint_off, joint_axis, point_pos, point_rad, spheres};
+  const size_t cnt[5] = {B * d * 3, B * d * 3, B * K * 3, B * K, B * O * 4};
+  for (int a = 0; a < 5; a++)
+    for (size_t k = 0; k < cnt[a]; k++)
+      if (!std::isfinite(arr[a][k])) { sco_set_error("sco_sqp_load_spatial: non-finite number"); return SCO_ERR_ARG; }
+  for (size_t k = 0; k < B * d; k++) {
+    const double *a = joint_axis + 3 * k;
+    if (fabs(sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) - 1.0) > 1e-9) { sco_set_error("sco_sqp_load_spatial: joint axes must be unit vectors"); return SCO_ERR_ARG; }
+  }
+  for (size_t k = 0; k < B * K; k++)
+    if (point_rad[k] < 0.0) { sco_set_error("sco_sqp_load_spatial: negative radius"); return SCO_ERR_ARG; }
+  for (size_t k = 0; k < B * O; k++)
+    if (spheres[4 * k + 3] < 0.0) { sco_set_error("sco_sqp_load_spatial: negative radius"); return SCO_ERR_ARG; }
+  SCO_ON_DEVICE(h->device);
+  double *dst[5] = {s.sp_off, s.sp_axis, s.sp_pos, s.sp_rad, s.sp_sph};
+  for (int a = 0; a < 5; a++) SCO_HIP(hipMemcpyAsync(dst[a], arr[a], cnt[a] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  SCO_HIP(hipStreamSynchronize(h->stream));
+  h->spatial_loaded = true; h->solved = false;
   return SCO_OK;
 }
 
@@ -1499,7 +1540,8 @@ static int sqp_check_state(const sco_sqp *h, const sco_sqp_params *params, const
       : ((fam & SCO_FAM_FLAG_JOINT_LIMITS) && !h->jl_loaded) ? "sco_sqp_load_joint_limits"
       : (h->d.m_gen && !h->gen_loaded) ? "sco_sqp_load_linear_rows"
       : ((fam & 15) == SCO_FAM_STATE_PROGRAM && !h->prog_loaded) ? "sco_sqp_load_program"
-      : ((fam & 15) == SCO_FAM_STATE_QUADRATIC && !h->quad_loaded) ? "sco_sqp_load_quadratic" : nullptr;
+      : ((fam & 15) == SCO_FAM_STATE_QUADRATIC && !h->quad_loaded) ? "sco_sqp_load_quadratic"
+      : ((fam & 15) == SCO_FAM_ARM_SPATIAL && !h->spatial_loaded) ? "sco_sqp_load_spatial" : nullptr;
   if (missing) { sco_set_error(std::string("sco_sqp_solve: call ") + missing + " first"); return SCO_ERR_STATE; }
   return SCO_OK;
 }

@@ -21,6 +21,7 @@ int sqp_check_desc(const sco_trajopt_desc *desc, int n_rows, const int *row_ptr,
   }
   const int family = desc->family, fam = family & 15, span = desc->span > 0 ? desc->span : 1, dof = desc->dof;
   const bool arm = fam == SCO_FAM_ARM_CIRCLES || fam == SCO_FAM_ARM_REACH, pointfam = fam == SCO_FAM_POINT_CIRCLES;
+  const bool spatial = fam == SCO_FAM_ARM_SPATIAL;
   const bool progfam = fam == SCO_FAM_STATE_PROGRAM, statefam = fam == SCO_FAM_STATE_QUADRATIC || progfam;
   const bool ee = (family & SCO_FAM_FLAG_EE_COST) != 0, objprog = (family & SCO_FAM_FLAG_OBJ_PROGRAM) != 0;
   const bool objblk = (family & SCO_FAM_FLAG_OBJ_BLOCK) != 0, objwide = (family & SCO_FAM_FLAG_OBJ_WIDE) != 0;
@@ -34,7 +35,9 @@ int sqp_check_desc(const sco_trajopt_desc *desc, int n_rows, const int *row_ptr,
       desc->horizon < 2 || desc->horizon > 256,
       // family and flags
       (family & ~known_flags) != 0,
-      !arm && !pointfam && !statefam,
+      !arm && !pointfam && !statefam && !spatial,
+      // the spatial arm: obstacle rows and the linear-row flags only (no 3-D reach equality or end-effector term)
+      spatial && (dof > SPATIAL_DMAX || ee),
       ee && dof > OBJ_DMAX,
       (family & SCO_FAM_FLAG_ACC_COST) && desc->horizon < 3,
       pointfam && (desc->n_points != 1 || dof < 2 || ee),
@@ -82,7 +85,7 @@ SqpLayout sqp_layout_build(const sco_trajopt_desc &desc, int m_gen, const int *g
   L.R = R; L.n_x = n_x; L.n_slack = n_slack; L.n = n; L.m_lin = m_lin; L.m_nl = m_nl; L.m = m;
   L.NB = NBt + (reach ? 1 : 0); L.RM = std::max(R, NE) + (cost ? 1 : 0);     // + the objective term's value
   L.point = fam == SCO_FAM_POINT_CIRCLES ? ROWS_POINT : fam == SCO_FAM_STATE_QUADRATIC ? ROWS_QUADRATIC :
-            fam == SCO_FAM_STATE_PROGRAM ? ROWS_PROGRAM : ROWS_ARM;
+            fam == SCO_FAM_STATE_PROGRAM ? ROWS_PROGRAM : fam == SCO_FAM_ARM_SPATIAL ? ROWS_SPATIAL : ROWS_ARM;
   L.cost = oblk ? OBJ_BLOCK : (desc.family & SCO_FAM_FLAG_OBJ_PROGRAM) ? OBJ_PROGRAM : cost ? OBJ_EE : OBJ_NONE;
   L.acc = acc ? 1 : 0;
   // linear rows of column (t, j), ascending: pin, velocity rows "theta[t] - theta[t-1] <= vmax" (+1),

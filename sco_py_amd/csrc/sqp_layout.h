@@ -11,6 +11,7 @@
 #include <vector>
 
 #define OBJ_DMAX 16           // widest objective term of the per-thread eigenvalue sweep (min_eig_jacobi)
+#define SPATIAL_DMAX 16       // most joints of SCO_FAM_ARM_SPATIAL
 #define SCO_STATE_MAX 32      // widest state of a constraint block of the program family (span x dof)
 
 // SqpDev::point -- the family of the non-linear rows (sco_trajopt_desc::family & 15)
@@ -18,7 +19,8 @@ enum RowFamily {
   ROWS_ARM = 0,               // SCO_FAM_ARM_CIRCLES / SCO_FAM_ARM_REACH: link points of the planar arm against circles
   ROWS_POINT = 1,             // SCO_FAM_POINT_CIRCLES: distances of the point x[0:2] itself (no arm kinematics)
   ROWS_QUADRATIC = 2,         // SCO_FAM_STATE_QUADRATIC: general quadratic rows with per-problem coefficients
-  ROWS_PROGRAM = 3            // SCO_FAM_STATE_PROGRAM: rows as postfix programs (shared) over the state and per-problem parameters
+  ROWS_PROGRAM = 3,           // SCO_FAM_STATE_PROGRAM: rows as postfix programs (shared) over the state and per-problem parameters
+  ROWS_SPATIAL = 4            // SCO_FAM_ARM_SPATIAL: link spheres of a spatial serial arm against sphere obstacles
 };
 // SqpDev::cost -- the non-quadratic objective term
 enum ObjKind {

@@ -90,6 +90,71 @@ __device__ __forceinline__ double arm_ee_cost(const double *th, const double *le
   return w * (ex * ex + ey * ey);
 }
 
+// SCO_FAM_ARM_SPATIAL: forward kinematics of a spatial serial arm of revolute joints up to link point (lk, pos).  Joint i:
+//   p <- p + R off_i;   R <- R Rod(ax_i, theta_i),  Rod = I + sin K + (1 - cos) K^2,  K = skew(ax_i)
+// and the point rides on the frame of joint lk behind that joint's rotation, p_k = p + R pos.  Every sum and product is the
+// one sco_py_amd/workloads.py:_spatial_chain writes, in its order and without fused multiply-adds (NumPy has none): a
+// Jacobian entry that differs in its last bit can move the iteration count of a slowly converging QP by many termination
+// checks.  `pert` >= 0 adds `h` to joint `pert`; jg >= 0 also returns that joint's world axis and origin (aj, oj).
+struct Vec3 { double x, y, z; };
+__device__ __forceinline__ Vec3 spatial_point(const double *th, const double *off, const double *axis, int lk, const double *pos,
+                                              int pert, double h, int jg, Vec3 *aj, Vec3 *oj) {
+#pragma clang fp contract(off)
+  double r00 = 1.0, r01 = 0.0, r02 = 0.0, r10 = 0.0, r11 = 1.0, r12 = 0.0, r20 = 0.0, r21 = 0.0, r22 = 1.0;
+  double px = 0.0, py = 0.0, pz = 0.0;
+  for (int i = 0; i <= lk; i++) {
+    const double ox = off[3 * i], oy = off[3 * i + 1], oz = off[3 * i + 2];
+    const double ax = axis[3 * i], ay = axis[3 * i + 1], az = axis[3 * i + 2];
+    px = px + ((r00 * ox + r01 * oy) + r02 * oz);
+    py = py + ((r10 * ox + r11 * oy) + r12 * oz);
+    pz = pz + ((r20 * ox + r21 * oy) + r22 * oz);
+    if (i == jg) {
+      aj->x = (r00 * ax + r01 * ay) + r02 * az; aj->y = (r10 * ax + r11 * ay) + r12 * az; aj->z = (r20 * ax + r21 * ay) + r22 * az;
+      oj->x = px; oj->y = py; oj->z = pz;
+    }
+    double a = th[i];
+    if (i == pert) a += h;
+    double s, c;
+    sincos(a, &s, &c);
+    const double v = 1.0 - c;
+    const double xy = v * (ax * ay), xz = v * (ax * az), yz = v * (ay * az);
+    const double sx = s * ax, sy = s * ay, sz = s * az;
+    const double m00 = 1.0 - v * (ay * ay + az * az), m01 = xy - sz, m02 = xz + sy;
+    const double m10 = xy + sz, m11 = 1.0 - v * (ax * ax + az * az), m12 = yz - sx;
+    const double m20 = xz - sy, m21 = yz + sx, m22 = 1.0 - v * (ax * ax + ay * ay);
+    const double n00 = (r00 * m00 + r01 * m10) + r02 * m20, n01 = (r00 * m01 + r01 * m11) + r02 * m21, n02 = (r00 * m02 + r01 * m12) + r02 * m22;
+    const double n10 = (r10 * m00 + r11 * m10) + r12 * m20, n11 = (r10 * m01 + r11 * m11) + r12 * m21, n12 = (r10 * m02 + r11 * m12) + r12 * m22;
+    const double n20 = (r20 * m00 + r21 * m10) + r22 * m20, n21 = (r20 * m01 + r21 * m11) + r22 * m21, n22 = (r20 * m02 + r21 * m12) + r22 * m22;
+    r00 = n00; r01 = n01; r02 = n02; r10 = n10; r11 = n11; r12 = n12; r20 = n20; r21 = n21; r22 = n22;
+  }
+  Vec3 p;
+  p.x = px + ((r00 * pos[0] + r01 * pos[1]) + r02 * pos[2]);
+  p.y = py + ((r10 * pos[0] + r11 * pos[1]) + r12 * pos[2]);
+  p.z = pz + ((r20 * pos[0] + r21 * pos[1]) + r22 * pos[2]);
+  return p;
+}
+// row (k, o) of one timestep block: g = (r_o + rad_k) - || p_k(theta) - c_o ||, sphere = (cx, cy, cz, r)
+__device__ __forceinline__ double spatial_row(const double *th, const double *off, const double *axis, int lk, const double *pos,
+                                              double rad, const double *sphere, int pert, double h) {
+#pragma clang fp contract(off)
+  const Vec3 p = spatial_point(th, off, axis, lk, pos, pert, h, -1, nullptr, nullptr);
+  const double dx = p.x - sphere[0], dy = p.y - sphere[1], dz = p.z - sphere[2];
+  return (sphere[3] + rad) - sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// analytic d g / d theta_j of the same row from the geometric Jacobian: d p_k / d theta_j = a_j x (p_k - o_j) with joint j's
+// world axis a_j and world origin o_j; exactly 0 for a joint behind the point's link
+__device__ __forceinline__ double spatial_row_grad(const double *th, const double *off, const double *axis, int lk, const double *pos,
+                                                   const double *sphere, int j) {
+#pragma clang fp contract(off)
+  if (j > lk) return 0.0;
+  Vec3 a, o;
+  const Vec3 p = spatial_point(th, off, axis, lk, pos, -1, 0.0, j, &a, &o);
+  const double ex = p.x - o.x, ey = p.y - o.y, ez = p.z - o.z;
+  const double cx = a.y * ez - a.z * ey, cy = a.z * ex - a.x * ez, cz = a.x * ey - a.y * ex;
+  const double dx = p.x - sphere[0], dy = p.y - sphere[1], dz = p.z - sphere[2];
+  return -((dx * cx + dy * cy) + dz * cz) / sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
 // Richardson extrapolation of a central-difference ladder (halving steps): sco_py_amd/numdiff.py:_richardson
 __device__ __forceinline__ double richardson(double (&tab)[FD_LEVELS]) {
   double p4 = 4.0;
@@ -150,7 +215,8 @@ __device__ __forceinline__ RowRef row_ref(int e, const RowLay &L) {
 
 struct RowCtx { const double *len, *obs, *target; const int *point_link; const double *point_frac; int d, O, point;      // point: RowFamily
                 const double *qQ, *qa, *qc;         // SCO_FAM_STATE_QUADRATIC: this problem's row coefficients (ROWS_QUADRATIC)
-                const int *pw, *pptr; const double *pconst, *ppar; int par_step, R1; };   // SCO_FAM_STATE_PROGRAM (ROWS_PROGRAM): words, row starts, constants, this problem's parameters (block t: ppar + t * par_step)
+                const int *pw, *pptr; const double *pconst, *ppar; int par_step, R1;     // SCO_FAM_STATE_PROGRAM (ROWS_PROGRAM): words, row starts, constants, this problem's parameters (block t: ppar + t * par_step)
+                const double *joff, *jaxis, *ppos, *prad, *sph; };   // SCO_FAM_ARM_SPATIAL (ROWS_SPATIAL): this problem's joint offsets and axes [d][3], link points [K][3] and their radii [K], spheres [O][4]
 // (for the state families `d` is the dimension of a BLOCK's state, span x dof)
 
 // SCO_FAM_STATE_PROGRAM: value of program `o` at th, up to two coordinates perturbed (finite differences)
@@ -213,6 +279,8 @@ __device__ __forceinline__ double prog_dual(const RowCtx &c, const double *par, 
 __device__ __forceinline__ double row_value(const RowCtx &c, const RowRef &q, const double *th, int pert, double h) {
   if (q.eq == ROW_REACH_EQ) return arm_ee(th, c.len, c.d, q.r, pert, h);
   const int kp = q.r / c.O, o = q.r % c.O;
+  if (c.point == ROWS_SPATIAL)                            // SCO_FAM_ARM_SPATIAL: link sphere kp against sphere o
+    return spatial_row(th, c.joff, c.jaxis, c.point_link[kp], c.ppos + 3 * kp, c.prad[kp], c.sph + 4 * o, pert, h);
   if (c.point == ROWS_PROGRAM) {                          // SCO_FAM_STATE_PROGRAM: the row's postfix program; r04: behind R1 circle rows of the point x[0:2]
     if (q.r < c.R1) {
       const double dx = th[0] + (pert == 0 ? h : 0.0) - c.obs[3 * q.r], dy = th[1] + (pert == 1 ? h : 0.0) - c.obs[3 * q.r + 1];
@@ -240,6 +308,7 @@ __device__ __forceinline__ double row_value(const RowCtx &c, const RowRef &q, co
 __device__ __forceinline__ double row_grad(const RowCtx &c, const RowRef &q, const double *th, int j) {
   if (q.eq == ROW_REACH_EQ) return arm_ee_grad(th, c.len, c.d, q.r, j);
   const int kp = q.r / c.O, o = q.r % c.O;
+  if (c.point == ROWS_SPATIAL) return spatial_row_grad(th, c.joff, c.jaxis, c.point_link[kp], c.ppos + 3 * kp, c.sph + 4 * o, j);
   if (c.point == ROWS_PROGRAM) {                          // forward-mode differentiation of the row's program (r03); circle rows in closed form
     if (q.r < c.R1) {
       if (j > 1) return 0.0;
@@ -260,6 +329,11 @@ __device__ __forceinline__ double row_grad(const RowCtx &c, const RowRef &q, con
     return -(j == 0 ? dx : dy) / sqrt(dx * dx + dy * dy);
   }
   return arm_row_grad(th, c.len, c.point_link[kp], c.point_frac[kp], c.obs[3 * o], c.obs[3 * o + 1], j);
+}
+// true when row q does not depend on coordinate j at all, so that its central differences are exactly 0 and need not be
+// run: a joint behind the link a point of the spatial arm rides on
+__device__ __forceinline__ bool row_ignores(const RowCtx &c, const RowRef &q, int j) {
+  return c.point == ROWS_SPATIAL && j > c.point_link[q.r / c.O];
 }
 // non-quadratic objective term of a timestep with up to two perturbed coordinates: the arm's end-effector term
 // (SCO_FAM_FLAG_EE_COST) or the objective program (SCO_FAM_FLAG_OBJ_PROGRAM / SCO_FAM_FLAG_OBJ_BLOCK: program index O; for a

@@ -64,6 +64,29 @@ class ArmCirclesExpr(DeviceExpr):
         return self.point_link.shape[0] * self.obstacles.shape[0]
 
 
+class SpatialArmSpheresExpr(DeviceExpr):
+    """SCO_FAM_ARM_SPATIAL: g[k * O + o](theta) = r_o + rad_k - || p_k(theta) - c_o || for the K link spheres of a spatial
+    serial arm of revolute joints (``workloads.spatial_points``) and O sphere obstacles (cx, cy, cz, radius); theta = the
+    joint angles of ONE timestep (d, 1)."""
+    kind = "arm_spatial"
+
+    def __init__(self, joint_off, joint_axis, point_link, point_pos, point_rad, spheres, analytic=False):
+        self.joint_off = _f64(joint_off).reshape(-1, 3)
+        self.joint_axis = _f64(joint_axis).reshape(-1, 3)
+        self.point_link = np.array(point_link, dtype=np.int32).ravel()
+        self.point_pos = _f64(point_pos).reshape(-1, 3)
+        self.point_rad = _f64(point_rad).ravel()
+        self.spheres = _f64(spheres).reshape(-1, 4)
+        assert self.joint_off.shape == self.joint_axis.shape and self.point_pos.shape[0] == self.point_link.shape[0] == self.point_rad.shape[0]
+        geo = lambda: (self.joint_off, self.joint_axis, self.point_link, self.point_pos, self.point_rad, self.spheres)
+        f = lambda x: wl.spatial_dist(x.ravel(), *geo()).reshape(-1, 1)
+        g = (lambda x: wl.spatial_dist_jac(x.ravel(), *geo())) if analytic else None
+        super(SpatialArmSpheresExpr, self).__init__(f, g)
+
+    def n_rows(self):
+        return self.point_link.shape[0] * self.spheres.shape[0]
+
+
 class ArmReachExpr(DeviceExpr):
     """SCO_FAM_ARM_REACH: end-effector position (2 rows) of the planar arm; use inside ``EqExpr(expr, target)`` on the
     last timestep."""

@@ -158,7 +158,7 @@ def _compile(prob):
     key_fam = None
     for t, bl in enumerate(blocks):
         kinds = [(type(be.expr), be.expr.expr.kind) for be in bl]
-        if fam in ("arm_circles", "point_circles"):
+        if fam in ("arm_circles", "point_circles", "arm_spatial"):
             if kinds != [(ex.LEqExpr, fam)]:
                 _no("every timestep needs exactly one LEqExpr block of the %s family" % fam)
         elif kinds not in ([(ex.LEqExpr, fam)], [(ex.LEqExpr, fam), (ex.EqExpr, fam)], [(ex.EqExpr, fam)]):
@@ -183,6 +183,20 @@ def _compile(prob):
         key_fam = ("arm", pr["K"], pr["O"], tuple(e0.point_link.tolist()), tuple(e0.point_frac.tolist()))
     elif reach_be is not None:
         _no("the end-effector equality belongs to the arm family")
+    elif fam == "arm_spatial":
+        names = ("joint_off", "joint_axis", "point_link", "point_pos", "point_rad", "spheres")
+        for bl in blocks:
+            e = bl[0].expr.expr
+            if not all(_same(getattr(e, k), getattr(e0, k)) for k in names):
+                _no("per-timestep geometry of the spatial arm (the device template has per-problem geometry)")
+        if e0.joint_off.shape[0] != d:
+            _no("joint count differs from the state dimension")
+        if np.any(e0.point_link < 0) or np.any(e0.point_link >= d):
+            _no("a link point rides on a joint the arm does not have")
+        pr.update(K=int(e0.point_link.shape[0]), O=int(e0.spheres.shape[0]), point_link=e0.point_link.copy(),
+                  point_frac=np.ones(e0.point_link.shape[0]), obstacles=np.zeros((e0.spheres.shape[0], 3)), spatial=True,
+                  **{k: getattr(e0, k).copy() for k in wl.SPATIAL_KEYS})
+        key_fam = ("spatial", pr["K"], pr["O"], tuple(e0.point_link.tolist()))
     elif fam == "point_circles":
         for bl in blocks:
             if not _same(bl[0].expr.expr.obstacles, e0.obstacles):
@@ -473,6 +487,10 @@ def _stack(cps):
         a["reach"] = True; a["target"] = st("target")
     if p0.get("point"):
         a["point"] = True
+    if p0.get("spatial"):
+        a["spatial"] = True
+        for k in wl.SPATIAL_KEYS:
+            a[k] = st(k)
     if p0.get("row_program") is not None:
         a["row_program"] = p0["row_program"]; a["row_params"] = st("row_params")
     if p0.get("quad_Q") is not None:
@@ -517,7 +535,7 @@ def run_compiled(cps, params, qp_settings, device=0):
                              point=bool(a.get("point")), quadratic=a.get("quad_Q") is not None,
                              program=a.get("row_program") if a.get("row_program") is not None else False,
                              n_eq_rows=a.get("quad_n_eq", 0), lin_rows=a.get("lin_rows"), circle_rows=a.get("circle_rows", 0),
-                             acc_cost=a.get("acc_w") is not None)
+                             acc_cost=a.get("acc_w") is not None, spatial=bool(a.get("spatial")))
     _HANDLES[hk] = tb                       # most recently used last
     while len(_HANDLES) > _HANDLE_CAP:
         _HANDLES.pop(next(iter(_HANDLES))).close()
@@ -528,7 +546,8 @@ def run_compiled(cps, params, qp_settings, device=0):
             cost_weight=a.get("cost_weight"), cost_target=a.get("cost_target"),
             quad_Q=a.get("quad_Q"), quad_a=a.get("quad_a"), quad_c=a.get("quad_c"),
             row_program=a.get("row_program"), row_params=a.get("row_params"), obj_weights=a.get("obj_w"),
-            lin_vals=a.get("lin_vals"), lin_rhs=a.get("lin_rhs"), acc_weights=a.get("acc_w"))
+            lin_vals=a.get("lin_vals"), lin_rhs=a.get("lin_rhs"), acc_weights=a.get("acc_w"),
+            **{k: a.get(k) for k in wl.SPATIAL_KEYS})
     if a.get("groups") is not None:
         tb.set_groups(a["groups"])
     t1 = time.perf_counter()

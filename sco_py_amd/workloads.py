@@ -4,7 +4,7 @@ The reference ships no benchmark problems; this module defines the
 seeded planar-arm workload of SURVEY.md 8(d) in NumPy so that bench.py, the tests,
 the oracle and the golden-vector generators all hand the device kernels the same
 inputs.  The NumPy forward kinematics below are the definition of the device
-constraint families (SCO_FAM_ARM_CIRCLES / SCO_FAM_ARM_REACH / SCO_FAM_POINT_CIRCLES, csrc/sco_sqp.hip) and
+constraint families (SCO_FAM_ARM_CIRCLES / SCO_FAM_ARM_REACH / SCO_FAM_POINT_CIRCLES / SCO_FAM_ARM_SPATIAL, csrc/sqp_rows.h) and
 what a host-side `Expr(f)` of the same constraint evaluates.
 
 Problem i (``make_problem(i, ...)``):
@@ -114,6 +114,92 @@ def quad_rows_jac(x, Q, a, c):
     """Analytic Jacobian (R, d) of quad_rows (Q_r symmetric)."""
     x = np.asarray(x, dtype=np.float64).ravel()
     return a + np.einsum("rij,j->ri", Q, x)
+
+
+def _spatial_chain(theta, joint_off, joint_axis, upto, dtype=np.float64):
+    """Forward kinematics of the spatial arm (SCO_FAM_ARM_SPATIAL) through joint ``upto``: per joint i its world origin o_i,
+    its world axis a_i and the frame R_i behind its rotation (nine scalars, row-major).  Written scalar by scalar: this order of
+    operations is what csrc/sqp_rows.h:spatial_point follows.  ``dtype`` is the arithmetic's type (the tests screen seeds
+    with numpy.longdouble)."""
+    f = dtype
+    one = f(1.0)
+    r00, r01, r02, r10, r11, r12, r20, r21, r22 = one, f(0.0), f(0.0), f(0.0), one, f(0.0), f(0.0), f(0.0), one
+    px, py, pz = f(0.0), f(0.0), f(0.0)
+    origins, axes, frames = [], [], []
+    for i in range(upto + 1):
+        ox, oy, oz = f(joint_off[i][0]), f(joint_off[i][1]), f(joint_off[i][2])
+        ax, ay, az = f(joint_axis[i][0]), f(joint_axis[i][1]), f(joint_axis[i][2])
+        px = px + ((r00 * ox + r01 * oy) + r02 * oz)
+        py = py + ((r10 * ox + r11 * oy) + r12 * oz)
+        pz = pz + ((r20 * ox + r21 * oy) + r22 * oz)
+        origins.append((px, py, pz))
+        axes.append(((r00 * ax + r01 * ay) + r02 * az, (r10 * ax + r11 * ay) + r12 * az, (r20 * ax + r21 * ay) + r22 * az))
+        a = f(theta[i])
+        s, c = np.sin(a), np.cos(a)
+        v = one - c
+        xy, xz, yz = v * (ax * ay), v * (ax * az), v * (ay * az)
+        sx, sy, sz = s * ax, s * ay, s * az
+        m00, m01, m02 = one - v * (ay * ay + az * az), xy - sz, xz + sy
+        m10, m11, m12 = xy + sz, one - v * (ax * ax + az * az), yz - sx
+        m20, m21, m22 = xz - sy, yz + sx, one - v * (ax * ax + ay * ay)
+        n00, n01, n02 = (r00 * m00 + r01 * m10) + r02 * m20, (r00 * m01 + r01 * m11) + r02 * m21, (r00 * m02 + r01 * m12) + r02 * m22
+        n10, n11, n12 = (r10 * m00 + r11 * m10) + r12 * m20, (r10 * m01 + r11 * m11) + r12 * m21, (r10 * m02 + r11 * m12) + r12 * m22
+        n20, n21, n22 = (r20 * m00 + r21 * m10) + r22 * m20, (r20 * m01 + r21 * m11) + r22 * m21, (r20 * m02 + r21 * m12) + r22 * m22
+        r00, r01, r02, r10, r11, r12, r20, r21, r22 = n00, n01, n02, n10, n11, n12, n20, n21, n22
+        frames.append((px, py, pz, r00, r01, r02, r10, r11, r12, r20, r21, r22))
+    return origins, axes, frames
+
+
+def _spatial_on_frame(frame, pos, dtype=np.float64):
+    px, py, pz, r00, r01, r02, r10, r11, r12, r20, r21, r22 = frame
+    x, y, z = dtype(pos[0]), dtype(pos[1]), dtype(pos[2])
+    return (px + ((r00 * x + r01 * y) + r02 * z), py + ((r10 * x + r11 * y) + r12 * z), pz + ((r20 * x + r21 * y) + r22 * z))
+
+
+def spatial_points(theta, joint_off, joint_axis, point_link, point_pos, dtype=np.float64):
+    """Positions (K, 3) of the K link points of a spatial serial arm of revolute joints for joint angles theta (d,): joint i
+    sits at joint_off[i] in its parent's frame and turns about the unit axis joint_axis[i] of its own frame,
+    p <- p + R off_i,  R <- R Rod(ax_i, theta_i); point k rides on the frame of joint point_link[k] behind that joint's
+    rotation, p_k = p + R point_pos[k]."""
+    theta = np.asarray(theta).ravel()
+    pl = [int(k) for k in np.asarray(point_link).ravel()]
+    _, _, frames = _spatial_chain(theta, joint_off, joint_axis, max(pl), dtype)
+    return np.array([_spatial_on_frame(frames[lk], point_pos[k], dtype) for k, lk in enumerate(pl)], dtype=dtype)
+
+
+def spatial_dist(theta, joint_off, joint_axis, point_link, point_pos, point_rad, spheres, dtype=np.float64):
+    """SCO_FAM_ARM_SPATIAL: g (K*O,) with g[k*O + o] = r_o + rad_k - ||p_k - c_o||, spheres (O, 4) = (cx, cy, cz, r).  The
+    result is float64 whatever ``dtype`` the kinematics ran in."""
+    p = spatial_points(theta, joint_off, joint_axis, point_link, point_pos, dtype)
+    K, O = p.shape[0], len(spheres)
+    g = np.zeros(K * O)
+    for k in range(K):
+        for o in range(O):
+            dx, dy, dz = p[k, 0] - dtype(spheres[o][0]), p[k, 1] - dtype(spheres[o][1]), p[k, 2] - dtype(spheres[o][2])
+            g[k * O + o] = (dtype(spheres[o][3]) + dtype(point_rad[k])) - np.sqrt((dx * dx + dy * dy) + dz * dz)
+    return g
+
+
+def spatial_dist_jac(theta, joint_off, joint_axis, point_link, point_pos, point_rad, spheres, dtype=np.float64):
+    """Analytic Jacobian (K*O, d) of spatial_dist from the geometric Jacobian: d p_k / d theta_j = a_j x (p_k - o_j) for the
+    joints j up to the point's link (world axis a_j, world origin o_j), exactly 0 behind it."""
+    theta = np.asarray(theta).ravel()
+    d = theta.shape[0]
+    pl = [int(k) for k in np.asarray(point_link).ravel()]
+    origins, axes, frames = _spatial_chain(theta, joint_off, joint_axis, max(pl), dtype)
+    K, O = len(pl), len(spheres)
+    J = np.zeros((K * O, d))
+    for k, lk in enumerate(pl):
+        p = _spatial_on_frame(frames[lk], point_pos[k], dtype)
+        for o in range(O):
+            dx, dy, dz = p[0] - dtype(spheres[o][0]), p[1] - dtype(spheres[o][1]), p[2] - dtype(spheres[o][2])
+            dist = np.sqrt((dx * dx + dy * dy) + dz * dz)
+            for j in range(lk + 1):
+                a, q = axes[j], origins[j]
+                ex, ey, ez = p[0] - q[0], p[1] - q[1], p[2] - q[2]
+                cx, cy, cz = a[1] * ez - a[2] * ey, a[2] * ex - a[0] * ez, a[0] * ey - a[1] * ex
+                J[k * O + o, j] = -((dx * cx + dy * cy) + dz * cz) / dist
+    return J
 
 
 def velocity_rows(d, T):
@@ -243,6 +329,47 @@ def make_quadratic_problem(i, d=2, T=20, O=3, noise=0.03, groups=None, vel_limit
         out["jlo"] = np.minimum(start, goal) - float(joint_limit)
         out["jhi"] = np.maximum(start, goal) + float(joint_limit)
     return out
+
+
+def make_spatial_problem(i, d=7, T=20, K=5, O=2, noise=0.05, groups=None, vel_limit=None, joint_limit=None):
+    """Seeded problem i of the spatial-arm family (SCO_FAM_ARM_SPATIAL): a serial arm of d revolute joints whose axes cycle
+    z, y, x (each tilted a little), links of length 1 / d with a small rise, K link spheres and O sphere obstacles that sit
+    near where the straight line between start and goal carries a point of the outer half of the arm.  Same dictionary
+    layout as make_problem (link_len, point_frac and obstacles are placeholders the family does not read) plus joint_off,
+    joint_axis, point_pos, point_rad, spheres.  Its own generator: no number of another workload depends on it."""
+    rng = np.random.default_rng(11000 + i)
+    start = rng.uniform(-np.pi / 2, np.pi / 2, size=d)
+    goal = rng.uniform(-np.pi / 2, np.pi / 2, size=d)
+    s = np.linspace(0.0, 1.0, T)[:, None]
+    x0 = (1 - s) * start[None, :] + s * goal[None, :] + noise * rng.standard_normal((T, d))
+    base = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [1.0, 0.0, 0.0]])
+    axis = base[np.arange(d) % 3] + 0.2 * rng.standard_normal((d, 3))
+    axis = axis / np.sqrt(np.sum(axis * axis, axis=1))[:, None]
+    off = np.zeros((d, 3))
+    off[1:, 0] = 1.0 / d; off[1:, 2] = 0.1 / d
+    point_link, frac = default_points(d, K)
+    pos = np.zeros((K, 3)); pos[:, 0] = frac / d
+    rad = rng.uniform(0.01, 0.03, size=K)
+    spheres = np.zeros((O, 4))
+    for o in range(O):
+        k = int(rng.integers(K // 2, K))
+        a = rng.uniform(0.25, 0.75)
+        spheres[o, :3] = spatial_points((1 - a) * start + a * goal, off, axis, point_link, pos)[k] + 0.04 * rng.standard_normal(3)
+        spheres[o, 3] = rng.uniform(0.06, 0.14)
+    out = dict(d=d, T=T, K=K, O=O, x0=x0.ravel(), start=start, goal=goal, link_len=np.full(d, 1.0 / d), point_link=point_link,
+               point_frac=frac, obstacles=np.zeros((O, 3)), reach=False, spatial=True, joint_off=off, joint_axis=axis,
+               point_pos=pos, point_rad=rad, spheres=spheres)
+    if groups is not None:
+        out["groups"] = block_groups(T, False, groups)
+    if vel_limit is not None:
+        out["vmax"] = float(vel_limit)
+    if joint_limit is not None:
+        out["jlo"] = np.minimum(start, goal) - float(joint_limit)
+        out["jhi"] = np.maximum(start, goal) + float(joint_limit)
+    return out
+
+
+SPATIAL_KEYS = ("joint_off", "joint_axis", "point_pos", "point_rad", "spheres")      # per-problem arrays of the spatial family
 
 
 _PROGRAMS = {}
@@ -657,10 +784,14 @@ def step_params(pr, t):
 
 
 def _make_problem(i, d=7, T=20, K=5, O=2, noise=0.05, reach=False, groups=None, vel_limit=None, joint_limit=None,
-                  ee_cost_weight=None, point=False, quadratic=False, program=False, variant=None, n_eq=0):
+                  ee_cost_weight=None, point=False, quadratic=False, program=False, variant=None, n_eq=0, spatial=False):
     """reach=True: the goal pin
     theta[T-1] = goal is replaced by the non-linear equality ee(theta[T-1]) = ee(goal)
     (EqExpr on an Expr: the abs-penalty path of prob.py:280-315); same random draws."""
+    if spatial:
+        if reach or ee_cost_weight is not None or point or quadratic or program:
+            raise ValueError("the spatial arm has obstacle rows and linear rows only")
+        return make_spatial_problem(i, d=d, T=T, K=K, O=O, noise=noise, groups=groups, vel_limit=vel_limit, joint_limit=joint_limit)
     if program:
         return make_program_problem(i, d=d, T=T, groups=groups, vel_limit=vel_limit, joint_limit=joint_limit, variant=variant)
     if quadratic:
@@ -711,6 +842,10 @@ def make_batch(B, first=0, **kw):
     extra = dict(reach=True, target=np.stack([p["target"] for p in probs])) if p0.get("reach") else {}
     if p0.get("point"):
         extra["point"] = True
+    if p0.get("spatial"):
+        extra["spatial"] = True
+        for k in SPATIAL_KEYS:
+            extra[k] = np.stack([p[k] for p in probs])
     if p0.get("row_program") is not None:
         extra["row_program"] = p0["row_program"]; extra["row_params"] = np.stack([p["row_params"] for p in probs])
     if p0.get("quad_Q") is not None:

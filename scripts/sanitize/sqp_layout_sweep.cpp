@@ -1,7 +1,7 @@
 // Stand-alone sweep of the SQP problem layout (csrc/sqp_layout.cpp) for a sanitizer build on the CPU:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined
 //       scripts/sanitize/sqp_layout_sweep.cpp sco_py_amd/csrc/sqp_layout.cpp -o sqp_layout_sweep && ./sqp_layout_sweep
-// Every family x flag set x dof 1 .. 4 x horizon 2 .. 6 and 256 x span 0 .. 4 x n_eq_rows 0 .. 2, with and without general
+// Every family (the spatial arm included) x flag set x dof 1 .. 4 x horizon 2 .. 6 and 256 x span 0 .. 4 x n_eq_rows 0 .. 2, with and without general
 // rows: sqp_check_desc, and for every accepted descriptor sqp_layout_build -- every index of Pi / Ai in range, Pp / Ap
 // monotone and ending at the vector sizes, every position table entry inside its value array.  Then sqp_check_program on
 // truncated and random word streams: whatever it accepts stays inside the stack and the operand arrays.
@@ -47,8 +47,8 @@ int main() {
   const int flag_bits[] = {SCO_FAM_FLAG_VEL_LIMITS, SCO_FAM_FLAG_JOINT_LIMITS, SCO_FAM_FLAG_EE_COST, SCO_FAM_FLAG_OBJ_PROGRAM,
                            SCO_FAM_FLAG_ACC_COST, SCO_FAM_FLAG_OBJ_BLOCK, SCO_FAM_FLAG_OBJ_WIDE, 2048};
   const int horizons[] = {2, 3, 4, 5, 6, 256};
-  long long descs = 0, accepted = 0;
-  for (int fam = 0; fam <= 6; fam++)
+  long long descs = 0, accepted = 0, spatial = 0;
+  for (int fam = 0; fam <= 7; fam++)
     for (int fl = 0; fl < 256; fl++) {
       int family = fam;
       for (int k = 0; k < 8; k++) if ((fl >> k) & 1) family |= flag_bits[k];
@@ -57,7 +57,7 @@ int main() {
           for (int span = 0; span <= 4; span++)
             for (int neq = 0; neq <= 2; neq++)
               for (int gen = 0; gen < 2; gen++) {
-                const sco_trajopt_desc desc = {3, dof, T, fam <= 2 ? 2 : 1, 2, family, 0, 0, span, neq};
+                const sco_trajopt_desc desc = {3, dof, T, (fam <= 2 || fam == SCO_FAM_ARM_SPATIAL) ? 2 : 1, 2, family, 0, 0, span, neq};
                 // general rows: an equality over the first and last variable, an inequality on the middle one
                 const int nx = dof * T, row_ptr[3] = {0, 2, 3}, col[3] = {0, nx - 1, nx / 2}, iseq[2] = {1, 0};
                 const char *err = nullptr;
@@ -69,11 +69,22 @@ int main() {
                 }
                 accepted++;
                 const SqpLayout L = sqp_layout_build(desc, gen ? 2 : 0, row_ptr, col, iseq);
+                if (fam == SCO_FAM_ARM_SPATIAL) {      // the planar arm's layout under another row model; linear-row flags and the acceleration term only
+                  spatial++;
+                  if (L.point != ROWS_SPATIAL || L.NE != 0 || L.cost != OBJ_NONE || span > 1 || neq != 0 ||
+                      (family & ~(15 | SCO_FAM_FLAG_VEL_LIMITS | SCO_FAM_FLAG_JOINT_LIMITS | SCO_FAM_FLAG_ACC_COST))) { printf("spatial family: accepted %d\n", family); return 1; }
+                }
                 if (!layout_ok(L, dof)) { printf("bad layout: family %d dof %d T %d span %d neq %d gen %d\n", family, dof, T, span, neq, gen); return 1; }
               }
     }
   printf("%lld descriptors, %lld accepted: every index, pointer and position of their layouts is in range\n", descs, accepted);
-  if (accepted == 0) return 1;
+  if (accepted == 0 || spatial == 0) return 1;
+  {   // the spatial arm's widest accepted arm, and one joint more
+    const sco_trajopt_desc wide = {1, SPATIAL_DMAX, 4, 3, 2, SCO_FAM_ARM_SPATIAL, 0, 0, 0, 0}, wider = {1, SPATIAL_DMAX + 1, 4, 3, 2, SCO_FAM_ARM_SPATIAL, 0, 0, 0, 0};
+    const char *err = nullptr;
+    if (sqp_check_desc(&wide, 0, nullptr, nullptr, nullptr, &err) != SCO_OK || sqp_check_desc(&wider, 0, nullptr, nullptr, nullptr, &err) != SCO_ERR_ARG ||
+        !layout_ok(sqp_layout_build(wide, 0, nullptr, nullptr, nullptr), SPATIAL_DMAX)) { printf("spatial family: joint limit\n"); return 1; }
+  }
 
   // malformed general-row patterns (each array as long as the well-formed one, so a refusal never reads past it)
   {
