@@ -120,6 +120,15 @@ int sco_qp_load(sco_qp *qp, const double *P_val, const double *q,
 /* Replace only l and u (trust-region retry: variable.py:43-45 changes nothing else). */
 int sco_qp_set_bounds(sco_qp *qp, const double *l, const double *u);
 
+/* Optional promise about the values of A, shared by the batch, meant for the SQP layer and callers that build the same
+ * trajectory penalty pattern: row i holds non-zeros only at the first row_width[i] variables of its timestep block, the
+ * block's variables counted in ascending variable index (variable t * dof + j is number j of block t).  row_width must
+ * be m long (nothing can check that); row_width[i] <= 0 promises nothing for the row, NULL withdraws every promise.  Only the hinge rows of a trajectory penalty QP are read, and only by the wavefront ADMM tier,
+ * which then skips the columns no row of a register slot can fill.  The values are tested on the device whenever a QP
+ * is factored: a problem that breaks the promise is solved by the row-local kernel, so a wrong hint costs speed, never
+ * a result.  SCO_WV_JW=0 in the environment makes the tier ignore the hint.  Takes effect with the next solve. */
+int sco_qp_set_row_widths(sco_qp *qp, const int *row_width);
+
 /* Solve all problems of the batch from a cold start (the reference rebuilds the
  * OSQP object for every QP, osqp_utils.py:195, so x0 = y0 = 0).
  * Outputs (any may be NULL): x[batch][n], y[batch][m], status[batch] (SCO_QP_*),
@@ -490,6 +499,17 @@ int sco_debug_mix_split(int live, int cus, int xcds, int slack, int per_cu);
  * index of component 0 of its r / x~ inside a block vector, index of its couplings}; all -1 for a position no sweep lane
  * holds. */
 int sco_debug_wv_gres_slot(int nstep, int pos, int out[5]);
+
+/* Jacobian widths of the wavefront tier (diagnostics; host arithmetic, no GPU needed; csrc/wv_plan.cpp: wv_plan_widths).
+ * sco_debug_wv_widths: the plan a handle would build for the pattern last given to sco_debug_plan_build, with the hint
+ * row_width[m] of sco_qp_set_row_widths (NULL: none) under SCO_WV_JW as it stands.  info[0] = the tier takes the pattern,
+ * info[1 .. 4] = the widths of the four hinge slots (0: a slot without rows), info[5] = the width profile the launch runs,
+ * four bits per slot, slot 0 lowest (0 = the generic kernel), info[6] = LDS bytes, info[7 .. 10] = <BS, NS, NV, NSTEP>,
+ * info[11] = lanes per block.
+ * sco_debug_sqp_row_widths: the hint the SQP layer hands to its penalty QP for this descriptor and point_link[n_points]:
+ * out[m] as row_width above; returns 1 when the family gives a hint, 0 when it gives none (out all 0). */
+int sco_debug_wv_widths(const int *row_width, int info[12]);
+int sco_debug_sqp_row_widths(const sco_trajopt_desc *desc, const int *point_link, int *out);
 
 /* The schedule of the SQP round loop on plain numbers (diagnostics; host arithmetic, no GPU needed; csrc/sqp_sched.h).  The
  * SCO_SQP_* environment variables are read as by sco_sqp_solve.

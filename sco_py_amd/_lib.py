@@ -75,6 +75,7 @@ ABI = {
     "sco_qp_destroy": (C.c_int, [C.c_void_p]),
     "sco_qp_load": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, _DP, _IP]),
     "sco_qp_set_bounds": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "sco_qp_set_row_widths": (C.c_int, [C.c_void_p, _IP]),
     "sco_qp_solve": (C.c_int, [C.c_void_p, C.POINTER(QpSettings), _DP, _DP, _IP, _IP, _DP]),
     "sco_qp_info": (C.c_int, [C.c_void_p, _IP]),
     "sco_qp_adaptive_info": (C.c_int, [C.c_void_p, _DP, _IP]),
@@ -108,6 +109,8 @@ ABI = {
     "sco_debug_sqp_mixed": (C.c_int, [C.c_void_p, _IP]),
     "sco_debug_mix_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sco_debug_wv_gres_slot": (C.c_int, [C.c_int, C.c_int, _IP]),
+    "sco_debug_wv_widths": (C.c_int, [_IP, _IP]),
+    "sco_debug_sqp_row_widths": (C.c_int, [C.POINTER(TrajoptDesc), _IP, _IP]),
     "sco_debug_sqp_schedule": (C.c_int, [_IP, _IP, _IP, _IP]),
     "sco_debug_stage_sweep": (C.c_int, [C.c_int, _DP, _DP, _IP, _DP]),
     "sco_debug_sqp_layout": (C.c_int, [C.POINTER(TrajoptDesc), C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _DP]),
@@ -235,6 +238,12 @@ class BatchedQP(object):
     def set_bounds(self, l, u):
         l = self._arr(l, (self.batch, self.m)); u = self._arr(u, (self.batch, self.m))
         check(load().sco_qp_set_bounds(self._h, dptr(l), dptr(u)))
+
+    def set_row_widths(self, row_width):
+        """Promise that row i of A holds non-zeros only in the first row_width[i] columns of its timestep block (<= 0: no
+        promise for the row; None withdraws every promise): sco_qp_set_row_widths."""
+        w = None if row_width is None else self._arr(row_width, (self.m,), np.int32)
+        check(load().sco_qp_set_row_widths(self._h, iptr(w)))
 
     def solve(self, settings=None):
         st = settings if settings is not None else default_qp_settings()

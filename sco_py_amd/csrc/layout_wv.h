@@ -15,6 +15,18 @@
 // today), else lane-private in LDS, NS x 512 doubles of the plan's request (qp_admm_wv_kernel says why).
 SCO_HD constexpr bool wv_jreg(int NS, int BS) { return WV_JREG && NS * BS <= 28; }
 
+// Jacobian WIDTHS of the hinge slots (wv_plan_widths; qp_admm_wv_kernel's JW).  A caller of the QP layer may promise that a
+// hinge row holds non-zeros only in its first w in-block columns (the serial-arm families: sqp_rows.h); slot q of the
+// kernel then needs jw[q] = the largest w over the rows the plan dealt to it, and every pass over the slot's Jacobian row
+// stops there.  A width profile is the four jw packed four bits each, slot 0 lowest; 0 = the generic kernel, every slot at
+// the full width BS.  The compiled profiles of the 7-wide NS = 4 kernels with three lanes per block, <7,4,3,10,3>: the
+// planner picks from this list, wv_launch (sco_admm_wv.hip) instantiates it and says how to add one.
+#define WV_JW_PACK(a, b, c, d) ((a) | ((b) << 4) | ((c) << 8) | ((d) << 12))
+#define WV_JW_PROFILES(X) \
+  X(3, 5, 7, 7)      /* 7 joints, 5 link points on links 1, 2, 4, 5, 6, two obstacles: the 7 x 20 arm workloads */ \
+  X(7, 6, 3, 2)      /* the same rows dealt to the slots by width (wv_plan_build's sort_width; SCO_WV_JSORT=0: row order, the line above) */
+SCO_HD constexpr int wv_jw(int JW, int q, int BS) { return JW ? (JW >> (4 * q)) & 15 : BS; }
+
 SCO_HD inline size_t wv_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }   // packed lower, j <= i
 
 // LDS layouts chosen against bank conflicts (r04 PMC: 42 % of the LDS cycles of the first version were conflicts, the LDS

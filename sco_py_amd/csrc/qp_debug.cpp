@@ -84,6 +84,21 @@ extern "C" int sco_debug_wv_stack_plan(int *info) {
   info[10] = wh.n_link; info[11] = wh.NL; info[12] = wh.per_cu; info[13] = wh.why; info[14] = wh.n_stack;
   return SCO_OK;
 }
+// Host-only: the plan of a handle (link rows allowed) with the Jacobian width hint row_width[m] (null: none), under SCO_WV_JW
+// as it stands.  info[0] fits, [1 .. 4] widths of the hinge slots, [5] the width profile of the launch (packed, 0 = generic),
+// [6] LDS bytes, [7 .. 10] <BS, NS, NV, NSTEP>, [11] lanes per block
+extern "C" int sco_debug_wv_widths(const int *row_width, int info[12]) {
+  if (!info) return SCO_ERR_ARG;
+  WvHost wh;
+  const QpCreateEnv env = qp_create_env();
+  const bool ok = wv_plan_build(g_dbg_plan, wh, true, env.wv_jsort && !env.wv_jw_off ? row_width : nullptr);
+  if (ok) wv_plan_widths(wh, row_width, env.wv_jw_off);
+  info[0] = ok ? 1 : 0;
+  for (int q = 0; q < 4; q++) info[1 + q] = wh.jw[q];
+  info[5] = wh.jw_profile; info[6] = (int)wh.lds_bytes; info[7] = wh.BS; info[8] = wh.NS; info[9] = wh.NV; info[10] = wh.NSTEP;
+  info[11] = wh.lpb;
+  return SCO_OK;
+}
 // Host-only: the structured global-memory plan of that pattern.  info[0] fits, [1] block order, [2] blocks, [3] block normal
 // matrices on the matrix cores, [4] why not (BtHost::mf_why), [5] LDS bytes
 extern "C" int sco_debug_bt_plan(int *info) {

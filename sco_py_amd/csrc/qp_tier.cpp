@@ -15,6 +15,8 @@ QpCreateEnv qp_create_env() {
   e.rl_closed = on("SCO_QP_RL_ALIGNED") || on("SCO_QP_RL_CLOSED"); e.rl_lay8 = on("SCO_QP_RL_LAY8");
   { const char *v = getenv("SCO_QP_RL_SPLIT"); e.rl_split_off = v && v[0] == '0'; }
   e.debug_plan = getenv("SCO_DEBUG_PLAN") != nullptr;
+  { const char *v = getenv("SCO_WV_JW"); e.wv_jw_off = v && v[0] == '0'; }
+  { const char *v = getenv("SCO_WV_JSORT"); e.wv_jsort = !(v && v[0] == '0'); }
   return e;
 }
 

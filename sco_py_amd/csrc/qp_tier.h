@@ -15,7 +15,7 @@
 #define SCO_FACTOR_BLOCK 1024   // threads of the factor kernels (qp_sweep_kernel, qp_factor_kernel)
 
 // The create-time switches, read once per sco_qp_create (qp_create_env).  Each is on only when the variable's first
-// character is '1', but for the last two.
+// character is '1', but for the last four.
 struct QpCreateEnv {
   bool factor_cholesky = false;  // SCO_QP_FACTOR_CHOLESKY: W by Cholesky + triangular inverse (cross-check)
   bool no_elim = false;          // SCO_QP_NO_ELIM: no variable is eliminated (dense core of order n)
@@ -28,6 +28,8 @@ struct QpCreateEnv {
   bool rl_lay8 = false;          // SCO_QP_RL_LAY8: 8 column groups of the W tile with the open assignment
   bool rl_split_off = false;     // SCO_QP_RL_SPLIT: on only at '0' -- a column's pairs all on the owner lane
   bool debug_plan = false;       // SCO_DEBUG_PLAN: on when set -- the closed assignment prints its components to stderr
+  bool wv_jsort = true;          // SCO_WV_JSORT: off only at '0' -- with a width hint, a block's hinge rows are dealt to the slots widest first (wv_plan_build)
+  bool wv_jw_off = false;        // SCO_WV_JW: on only at '0' -- the wavefront tier ignores Jacobian width hints (wv_plan_widths)
 };
 QpCreateEnv qp_create_env();
 

@@ -75,13 +75,25 @@ struct WvHost {
   // stacked rows (single rows of a core variable other than its last one, held in the variable slot's free link slots with an
   // empty partner: joint limits).  NL = WV_NL whenever n_link + n_stack > 0
   int n_stack = 0;
+  // Jacobian widths (wv_plan_widths): jw[q] = leading in-block columns of hinge slot q that may hold a non-zero, by the
+  // caller's hint (bs without one); jw_profile = the compiled width profile the launch runs (packed, layout_wv.h: it
+  // dominates jw slot by slot; 0 = the generic kernel, every slot at the full width)
+  int jw[4] = {0, 0, 0, 0}, jw_profile = 0;
+  bool jsorted = false;                                  // the rows were dealt by width (wv_plan_build's sort_width)
 };
+// row_width[m]: for every row the count of leading in-block columns that may be non-zero, <= 0 = no promise (null: none for
+// any row).  Only hinge rows are read.  off (SCO_WV_JW=0): the widths are recorded, the generic profile runs.  The lane
+// tables, the LDS request and the row assignment stay as wv_plan_build left them.
+void wv_plan_widths(WvHost &wh, const int *row_width, bool off);
 #define WV_NL 2               // link slots per variable slot: two one-sided rows per joint and transition, or one two-sided row
 // why wv_plan_build refused a pattern (sco_debug_wv_link_plan, info[13])
 enum WvWhy { WV_OK = 0, WV_WHY_OTHER = 1, WV_WHY_LINKS_OFF = 2, WV_WHY_THIRD_LINK = 3, WV_WHY_SAME_BLOCK = 4, WV_WHY_FAR_BLOCKS = 5,
              WV_WHY_INDEX = 6, WV_WHY_THREE_CORE = 7, WV_WHY_LDS = 8, WV_WHY_SHAPE = 9,
              WV_WHY_STACKED = 10 };   // single rows of a variable beyond its free link slots, or beyond the extra-row lanes
-bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links);
+// sort_width[m] (may be null): a block's hinge rows are dealt to lanes and slots in descending order of their width
+// (wv_plan_widths' reading of an entry; rows of equal width keep their order) instead of row order: slot 0 gets the widest
+// rows.  A block's partial column sums then add in another order: results move at rounding level (SCO_WV_JSORT=0 keeps the row order).
+bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links, const int *sort_width = nullptr);
 
 // ---- big tier (sco_qp_big.hip): everything in HBM/L2, 1024 threads per problem
 struct BigHost {

@@ -72,6 +72,9 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #ifndef WV_HANDOVER
 #define WV_HANDOVER 1         // lane-swap hand-overs of the sweeps: the swap's two operands chosen so that no select and no copy follows
 #endif
+#ifndef WV_JWIDTH
+#define WV_JWIDTH 1           // 0 = every launch on the generic kernel whatever width profile the plan holds (scripts/build_ablate.py wv:WV_JWIDTH=0)
+#endif
 #if WV_VARIANT == 1
 #define WV_FMAC_DPP(acc, w, g, k) asm("v_fmac_f64 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(g))
 #endif
@@ -120,6 +123,9 @@ struct WvArgs {
   // solution in x / y; ad_interval > 0 = adaptive rho (the ADAPT instantiation): rho is rho_b[b], estimated again every
   // ad_interval iterations; when it must change the solve parks with the new value and smask[b] = rflag[b] = 1
   int warm, ad_interval; double ad_tol; double *rho_b; int *rflag, *smask, *nupd;
+  // the width profile of the launch (WvHost::jw_profile, packed: layout_wv.h; 0 = every hinge slot at the full width): read by
+  // the factor kernel's value test only, the ADMM kernel has it as a template argument
+  int jw;
 };
 
 // Wavefront-wide max / sum in registers, every lane ends with the result: wave_reduce_all of sco_lanes.h.
@@ -179,6 +185,13 @@ __global__ __launch_bounds__(WV_T) void qp_wv_factor_kernel(WvArgs a) {
       if (!(ls[h] < -WV_BIG) || rho[h] != rho_base || w[h] != wk) bad = 1;
       if (!(us[br] > WV_BIG) || ls[br] != 0.0 || rho[br] != rho_base || w[br] != 1) bad = 1;
       eh = E[h]; eb = E[br]; de = D[ev];
+      // a width profile runs only on rows that keep the caller's promise: a non-zero at or beyond the slot's width sends the
+      // problem to the row-local kernel like any other failed test (a wrong hint costs speed, never a result)
+      if (a.jw)
+        for (int k = wv_jw(a.jw, q, bs); k < bs; k++) {
+          const int jp = tab[(T.hjpos + q * 8 + k) * 64 + lane];
+          if (jp >= 0 && a.As[(size_t)b * a.nnzA + jp] != 0.0) bad = 1;
+        }
     }
     double *c = cst + (size_t)wv_cst_h(q) * 64 + lane;
     c[0] = h >= 0 ? 1.0 / eh : 0.0; c[64] = h >= 0 ? 1.0 / eb : 0.0; c[128] = h >= 0 ? 1.0 / de : 0.0;
@@ -426,9 +439,17 @@ constexpr int wv_slots(int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int 
 // A STACKED row (a single row of (t, k) in a link slot: joint limits) is that row without the partner entry: its coefficient
 // there is 0, so what it adds to the link vector, to A'y and to A dx at the partner's place is an exact zero -- also in the
 // last block, whose partner place is the dummy block.
-template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK>
+//
+// JW: the width profile (layout_wv.h; 0 = every slot at the full width BS).  Hinge slot q holds, loads and multiplies the
+// columns k < wv_jw(JW, q, BS) of its Jacobian row only: the others are exact zeros in every problem that reaches this
+// kernel (the factor kernel's value test), and fma(0, x, s) = s for finite x -- but for the sign of a zero sum, -0 + +0 = +0.
+// What remains keeps its order and form.
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK, int JW>
 __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
   constexpr bool ADAPT = (EXT & 2) != 0;
+  static_assert(JW == 0 || (wv_jreg(NS, BS) && NS <= 4), "width profiles: Jacobian rows in registers, four slots");
+  // column k of hinge slot q takes part (a constant once the slot loops are unrolled; the generic kernel has no such test)
+#define WV_COL(q, k) (JW == 0 || (k) < wv_jw(JW, q, BS))
   static_assert(!(LNK > 0 && ADAPT), "adaptive rho on link patterns stays on the row-local kernel (qp_launch_plan)");
   constexpr int NLK = LNK > 0 ? NV * LNK : 1;           // link slots of a lane
   constexpr bool LREG = wv_link_regs(BS);
@@ -539,7 +560,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int j0 = on ? tab0[(oHJPOS + q * 8 + 2 * k) * 64 + lane] : -1, j1 = on ? tab0[(oHJPOS + q * 8 + 2 * k + 1) * 64 + lane] : -1;
-      d2 v; v.x = j0 >= 0 ? As[j0] : 0.0; v.y = j1 >= 0 ? As[j1] : 0.0;
+      d2 v; v.x = j0 >= 0 && WV_COL(q, 2 * k) ? As[j0] : 0.0; v.y = j1 >= 0 && WV_COL(q, 2 * k + 1) ? As[j1] : 0.0;
       if (JREG) { hJ[q][2 * k] = v.x; hJ[q][2 * k + 1] = v.y; }
       else *(d2 *)(jl_p + (q * 4 + k) * 128) = v;
     }
@@ -657,7 +678,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       if (MODE) {
         double s = J[0] * xt[0];
 #pragma unroll
-        for (int k = 1; k < BS; k++) s = __builtin_fma(J[k], xt[k], s);
+        for (int k = 1; k < BS; k++) if (WV_COL(q, k)) s = __builtin_fma(J[k], xt[k], s);
         const double xte = h_ge[q] - (kinv * c2) * s;
         const double zth = __builtin_fma(ae, xte, s), ztb = ab * xte;
         // hinge row: l = -inf
@@ -699,7 +720,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       h_ge[q] = ge;
       const double tp = th - c2 * ge;
 #pragma unroll
-      for (int k = 0; k < BS; k++) part[k] = __builtin_fma(J[k], tp, part[k]);
+      for (int k = 0; k < BS; k++) if (WV_COL(q, k)) part[k] = __builtin_fma(J[k], tp, part[k]);
     }
     {
       d2 v0, v1, v2, v3;
@@ -1011,7 +1032,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
       }
       double s = J[0] * xc[0];
 #pragma unroll
-      for (int k = 1; k < BS; k++) s = __builtin_fma(J[k], xc[k], s);
+      for (int k = 1; k < BS; k++) if (WV_COL(q, k)) s = __builtin_fma(J[k], xc[k], s);
       if (h >= 0) {
         h_xe[q] = xg[ev] / Dg[ev];
         h_z[q] = s + h_ae[q] * h_xe[q]; h_zb[q] = h_ab[q] * h_xe[q];
@@ -1066,7 +1087,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
           }
           double s = J[0] * xc[0];
 #pragma unroll
-          for (int k = 1; k < BS; k++) s = __builtin_fma(J[k], xc[k], s);
+          for (int k = 1; k < BS; k++) if (WV_COL(q, k)) s = __builtin_fma(J[k], xc[k], s);
           const double ax = s + h_ae[q] * h_xe[q], axb = h_ab[q] * h_xe[q];
           const double eh = CKH(q, 0), eb = CKH(q, 1), de = CKH(q, 2);
           w_pri = fmax(w_pri, fmax(eh * fabs(ax - h_z[q]), eb * fabs(axb - h_zb[q])));
@@ -1081,7 +1102,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
             v_dua = fmax(v_dua, fabs(h_q[q] + aty)); v_dn = fmax(v_dn, fmax(fabs(h_q[q]), fabs(aty)));
           }
 #pragma unroll
-          for (int k = 0; k < BS; k++) part[k] = __builtin_fma(J[k], wy, part[k]);
+          for (int k = 0; k < BS; k++) if (WV_COL(q, k)) part[k] = __builtin_fma(J[k], wy, part[k]);
         }
         d2 v0, v1, v2, v3;
         v0.x = part[0]; v0.y = part[1]; v1.x = part[2]; v1.y = part[3]; v2.x = part[4]; v2.y = part[5]; v3.x = part[6]; v3.y = BS > 7 ? part[7] : 0.0;
@@ -1184,7 +1205,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
             const double wd = wc * dsv.h[q];
             nat = fmax(nat, CKH(q, 2) * fabs(h_ae[q] * wd + h_ab[q] * dsv.b[q]));      // the slack's column
 #pragma unroll
-            for (int k = 0; k < BS; k++) part[k] = __builtin_fma(J[k], wd, part[k]);
+            for (int k = 0; k < BS; k++) if (WV_COL(q, k)) part[k] = __builtin_fma(J[k], wd, part[k]);
           }
           d2 v0, v1, v2, v3;
           v0.x = part[0]; v0.y = part[1]; v1.x = part[2]; v1.y = part[3]; v2.x = part[4]; v2.y = part[5]; v3.x = part[6]; v3.y = BS > 7 ? part[7] : 0.0;
@@ -1265,7 +1286,7 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
             }
             double s2 = J[0] * dxb[0];
 #pragma unroll
-            for (int k = 1; k < BS; k++) s2 = __builtin_fma(J[k], dxb[k], s2);
+            for (int k = 1; k < BS; k++) if (WV_COL(q, k)) s2 = __builtin_fma(J[k], dxb[k], s2);
             const double adh = CKH(q, 0) * (s2 + h_ae[q] * dsv.e[q]), adb = CKH(q, 1) * (h_ab[q] * dsv.e[q]);
             if (h_on[q] && ((h_u[q] < WV_BIG && adh > thr) || adb < -thr)) badv = 1.0;     // hinge: l = -inf; its slack's bound row: [0, inf)
           }
@@ -1375,10 +1396,19 @@ __global__ __launch_bounds__(WV_T) void qp_admm_wv_kernel(WvArgs a) {
     }
   }
 }
+#undef WV_COL
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------------------------------------------------
+// The width profile a launch with these settings runs: the plan's, where an instantiation of it exists -- the parity kernel
+// and the one that may start warm; adaptive rho keeps the generic kernel (its 7-wide instantiations sit at the register limit
+// as they are: wv_gres_fits).  The factor kernel tests the values against the same answer.
+// A profiled kernel keeps its Jacobian rows in registers (wv_jreg: a -DWV_JREG=0 build has none and runs the generic one).
+static int wv_launch_jw(const WvHost &wh, const AdmmArgs &aa) {
+  return (WV_JWIDTH != 0 && wv_jreg(wh.NS, wh.BS) && !aa.adaptive) ? wh.jw_profile : 0;
+}
+
 static void wv_fill_args(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, const int *setup_mask, WvArgs &a) {
   const QpDev &d = aa.d;
   a.n = d.n; a.m = d.m; a.n_e = d.n_e; a.n_c = d.n_c; a.nnzA = d.nnzA; a.nnzP = d.nnzP;
@@ -1397,6 +1427,7 @@ static void wv_fill_args(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, 
   // (null without adaptive rho: only the ADAPT instantiation and the factor kernel's value test read them)
   a.rho_b = aa.adaptive ? d.rho_b : nullptr; a.rflag = aa.adaptive ? d.rflag : nullptr;
   a.smask = aa.adaptive ? d.smask : nullptr; a.nupd = aa.adaptive ? d.nupd : nullptr;
+  a.jw = wv_launch_jw(wh, aa);
 #ifdef WV_ABLATE
   { const char *ab = getenv("SCO_WV_ABLATE"); a.ablate = ab ? atoi(ab) : 0; }
 #else
@@ -1432,17 +1463,19 @@ int wv_launch_factor(const AdmmArgs &aa, const int *setup_mask, const WvHost &wh
   return SCO_OK;
 }
 
-template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK>
+template <int BS, int NS, int NV, int NSTEP, int LPB, int EXT, int LNK, int JW = 0>
 static int wv_launch_k(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
   static bool attr_done[64] = {};
-  SCO_LDS_ATTR((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK>), 64 * 1024, attr_done);
-  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK>), dim3(nwg), dim3(WV_T), lds, st, a);
+  SCO_LDS_ATTR((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK, JW>), 64 * 1024, attr_done);
+  hipLaunchKernelGGL((qp_admm_wv_kernel<BS, NS, NV, NSTEP, LPB, EXT, LNK, JW>), dim3(nwg), dim3(WV_T), lds, st, a);
   SCO_HIP(hipGetLastError());
   return SCO_OK;
 }
 
-template <int BS, int NS, int NV, int NSTEP, int LPB>
+template <int BS, int NS, int NV, int NSTEP, int LPB, int JW = 0>
 static int wv_launch_one(const WvArgs &a, int nwg, size_t lds, hipStream_t st) {
+  // a width profile: a link-free plan with fixed rho (wv_plan_widths, wv_launch_jw), cold or warm
+  if constexpr (JW != 0) return a.warm ? wv_launch_k<BS, NS, NV, NSTEP, LPB, 1, 0, JW>(a, nwg, lds, st) : wv_launch_k<BS, NS, NV, NSTEP, LPB, 0, 0, JW>(a, nwg, lds, st);
   // parity mode runs the instantiation without any code of the extensions; the adaptive one can start warm as well
   // (a plan with link rows has no adaptive instantiation: qp_launch_plan keeps such launches on the row-local kernel)
   if (a.NL) {
@@ -1464,7 +1497,23 @@ int wv_launch(const AdmmArgs &aa, const WvHost &wh, const WvDev &wd, hipStream_t
   const size_t lds = std::max(wh.lds_bytes, (size_t)36 * 1024);      // (36 KB: never a fifth workgroup on a CU)
   // (link rows at three lanes per block run on the run-time-lpb instantiation: <7,4,3,10,3> with link rows needs scratch,
   // profiles/wv_link_rows.md)
-  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3 && !wh.NL) return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);    // 7-DOF, 17 .. 20 timesteps
+  if (wh.NSTEP == 10 && wh.NS == 4 && wh.lpb == 3 && !wh.NL) {                                                          // 7-DOF, 17 .. 20 timesteps
+    // The width profiles of this kernel: one instantiation pair (cold, warm) per line of WV_JW_PROFILES (layout_wv.h), the one
+    // table the planner picks from (wv_plan_widths) and this switch is made of.  To add a profile, add its line there, then
+    // read the compiler's resource report for the two new kernels (-Rpass-analysis=kernel-resource-usage): no scratch, the
+    // occupancy of the generic twin, no more accumulation registers than it -- else the plans it would take stay generic.
+    if constexpr (wv_jreg(4, 7)) {
+      switch (a.jw) {
+#define X(w0, w1, w2, w3) case WV_JW_PACK(w0, w1, w2, w3): return wv_launch_one<7, 4, 3, 10, 3, WV_JW_PACK(w0, w1, w2, w3)>(a, nwg, lds, st);
+        WV_JW_PROFILES(X)
+#undef X
+        default: break;
+      }
+    }
+    if (a.jw) { sco_set_error("wv_launch: no instantiation of the plan's width profile"); return SCO_ERR_STATE; }
+    return wv_launch_one<7, 4, 3, 10, 3>(a, nwg, lds, st);
+  }
+  if (a.jw) { sco_set_error("wv_launch: no instantiation of the plan's width profile"); return SCO_ERR_STATE; }
   if (wh.NSTEP == 10 && wh.NS == 4) return wv_launch_one<7, 4, 3, 10, 0>(a, nwg, lds, st);
   if (wh.NSTEP == 10) return wv_launch_one<8, 2, 2, 10, 0>(a, nwg, lds, st);
   if (wh.NSTEP == 4) return wv_launch_one<8, 1, 1, 4, 0>(a, nwg, lds, st);

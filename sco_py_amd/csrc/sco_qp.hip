@@ -844,6 +844,29 @@ extern "C" int sco_qp_set_bounds(sco_qp *qp, const double *l, const double *u) {
   return SCO_OK;
 }
 
+// A promise about the values, not a part of the pattern: the plans keep their layout, the wavefront tier picks the width
+// profile its kernel runs (wv_plan_widths) and tests every problem's values against it when it factors them.  Host state
+// only; it holds from the next QP that is set up.
+extern "C" int sco_qp_set_row_widths(sco_qp *qp, const int *row_width) {
+  if (!qp) { sco_set_error("sco_qp_set_row_widths: null pointer"); return SCO_ERR_ARG; }
+  if (!qp->use_wv) return SCO_OK;
+  const QpCreateEnv env = qp_create_env();
+  const bool sort = env.wv_jsort && !env.wv_jw_off && row_width;
+  if (sort || qp->wv.jsorted) {
+    // SCO_WV_JSORT: the rows are dealt again, by width (or back to row order); same shape, so the new lane tables go into
+    // the place of the old ones on the device
+    WvHost nw;
+    if (wv_plan_build(qp->plan, nw, true, sort ? row_width : nullptr) && nw.tab.size() == qp->wv.tab.size()) {
+      SCO_ON_DEVICE(qp->device);
+      SCO_HIP(hipStreamSynchronize(qp->stream));
+      SCO_HIP(hipMemcpy((void *)qp->wvd.tab, nw.tab.data(), nw.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+      qp->wv = nw;
+    }
+  }
+  wv_plan_widths(qp->wv, row_width, env.wv_jw_off);
+  return SCO_OK;
+}
+
 int sco_qp_launch(sco_qp *qp, const sco_qp_settings *st, const int *active_dev, hipEvent_t mid) {
   return sco_qp_launch_sliced(qp, st, active_dev, active_dev, 0, mid, nullptr);
 }
@@ -1100,3 +1123,6 @@ extern "C" int sco_debug_qp_wv_iters(const sco_qp *qp, unsigned long long *out) 
   if (!qp || !out) return SCO_ERR_ARG;
   return sco_qp_wv_iters(qp, out);
 }
+// The width profile this handle's plan holds (packed, layout_wv.h; 0: the generic kernel, or no wavefront tier): what a
+// fixed-rho launch runs after sco_qp_set_row_widths.
+extern "C" int sco_debug_qp_wv_profile(const sco_qp *qp) { return qp && qp->use_wv ? qp->wv.jw_profile : 0; }

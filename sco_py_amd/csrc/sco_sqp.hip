@@ -1109,6 +1109,13 @@ extern "C" int sco_sqp_load(sco_sqp *h, const double *x0, const double *start, c
   SCO_HIP(hipMemcpyAsync((void *)s.point_link, point_link, s.K * sizeof(int), hipMemcpyHostToDevice, h->stream));
   SCO_HIP(hipMemcpyAsync((void *)s.point_frac, point_frac, s.K * sizeof(double), hipMemcpyHostToDevice, h->stream));
   SCO_HIP(hipStreamSynchronize(h->stream));
+  {
+    // the serial-arm families promise the penalty QP the widths of their hinge rows (sqp_row_widths); any other family
+    // withdraws what an earlier load may have promised
+    std::vector<int> w;
+    const bool hint = sqp_row_widths(s.point, s.S, s.d, s.O, s.R, s.NBt, s.m_lin, s.m, point_link, w);
+    if (int rc = sco_qp_set_row_widths(h->qp1, hint ? w.data() : nullptr)) return rc;
+  }
   h->loaded = true; h->solved = false;
   return SCO_OK;
 }
@@ -1891,6 +1898,16 @@ extern "C" int sco_debug_sqp_layout(const sco_trajopt_desc *desc, int n_rows, co
     if (vals) vals = std::copy(dv[k]->begin(), dv[k]->end(), vals);
   }
   return SCO_OK;
+}
+extern "C" int sco_debug_sqp_row_widths(const sco_trajopt_desc *desc, const int *point_link, int *out) {
+  const char *err = "";
+  if (int rc = sqp_check_desc(desc, 0, nullptr, nullptr, nullptr, &err)) { sco_set_error(err); return rc; }
+  if (!point_link || !out) { sco_set_error("sco_debug_sqp_row_widths: null pointer"); return SCO_ERR_ARG; }
+  const SqpLayout L = sqp_layout_build(*desc, 0, nullptr, nullptr, nullptr);
+  std::vector<int> w;
+  const bool hint = sqp_row_widths(L.point, L.S, desc->dof, desc->n_obstacles, L.R, L.NBt, L.m_lin, L.m, point_link, w);
+  std::copy(w.begin(), w.end(), out);
+  return hint ? 1 : 0;
 }
 extern "C" int sco_debug_sqp_check_program(const sco_trajopt_desc *desc, int n_circle_rows, int n_words, const int *words,
                                            const int *row_ptr, int n_consts, int n_params) {

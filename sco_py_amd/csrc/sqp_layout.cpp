@@ -186,6 +186,18 @@ SqpLayout sqp_layout_build(const sco_trajopt_desc &desc, int m_gen, const int *g
   return L;
 }
 
+bool sqp_row_widths(int point, int S, int dof, int O, int R, int NBt, int m_lin, int m, const int *point_link, std::vector<int> &out) {
+  out.assign(m, 0);
+  if ((point != ROWS_ARM && point != ROWS_SPATIAL) || S != 1 || O <= 0 || !point_link) return false;
+  // hinge rows block-major behind the linear rows, row (k, o) of a block at k O + o (the reach rows behind them: no promise)
+  for (int blk = 0; blk < NBt; blk++)
+    for (int r = 0; r < R; r++) {
+      const int lk = point_link[r / O];
+      out[m_lin + blk * R + r] = (lk >= 0 && lk < dof) ? lk + 1 : 0;
+    }
+  return true;
+}
+
 int sqp_check_program(int n_prog_rows, int cost, int ds, int dof, int n_words, const int *words, const int *row_ptr,
                       int n_consts, int n_params, const char **err) {
   auto refuse = [&](const char *text) { *err = text; return SCO_ERR_ARG; };

@@ -57,6 +57,13 @@ struct SqpLayout {
 // `desc` and the general rows' pattern (gen_ptr[m_gen + 1], gen_col, gen_iseq[m_gen]; m_gen may be 0) have passed sqp_check_desc
 SqpLayout sqp_layout_build(const sco_trajopt_desc &desc, int m_gen, const int *gen_ptr, const int *gen_col, const int *gen_iseq);
 
+// The Jacobian width hint of the penalty QP (sco_qp_set_row_widths): for the serial-arm families -- the planar arm with or
+// without the reach rows, the spatial arm -- the hinge row of link point k holds non-zeros only at the joints 0 ..
+// point_link[k] of its timestep (the family guarantee: sqp_rows.h), so its width is point_link[k] + 1.  out[m]: that for
+// every hinge row, 0 (no promise) for every other row; false and all 0 for a family without the guarantee.
+// (plain numbers of the layout: point = RowFamily, S = span, R = rows per block, NBt = blocks)
+bool sqp_row_widths(int point, int S, int dof, int O, int R, int NBt, int m_lin, int m, const int *point_link, std::vector<int> &out);
+
 // The programs of sco_sqp_load_program{,_steps}: n_prog_rows = n_obstacles - circle rows programs of a block's rows over
 // its ds numbers, then, for a program objective (`cost`), the objective term over ds (OBJ_BLOCK) or dof (OBJ_PROGRAM)
 // numbers.  All of row_ptr is checked before any word is read through it; every program is then run once symbolically

@@ -330,6 +330,14 @@ __device__ __forceinline__ double row_grad(const RowCtx &c, const RowRef &q, con
   }
   return arm_row_grad(th, c.len, c.point_link[kp], c.point_frac[kp], c.obs[3 * o], c.obs[3 * o + 1], j);
 }
+// THE SERIAL-ARM GUARANTEE (stated here once; sqp_row_widths of sqp_layout.cpp turns it into the width hint of the penalty
+// QP, the wavefront ADMM tier skips the columns it empties): in the planar and the spatial arm family the Jacobian entry of
+// a hinge row of link point k at a joint j > point_link[k] is EXACTLY 0.0 on every route.  Analytic: arm_row_grad and
+// spatial_row_grad return 0.0 there.  Central differences: arm_row never reads a joint behind the point's link, so both
+// ends of every difference are the same number and Richardson extrapolates zeros; the spatial arm's ladder is not run at
+// all (row_ignores).  The memo (cJ) hands back what one of these routes stored.  The reach rows see every joint: no
+// promise.  A family that cannot say this gives no hint.
+
 // true when row q does not depend on coordinate j at all, so that its central differences are exactly 0 and need not be
 // run: a joint behind the link a point of the spatial arm rides on
 __device__ __forceinline__ bool row_ignores(const RowCtx &c, const RowRef &q, int j) {

@@ -38,7 +38,7 @@ static int wv_why_no_blocks(const QpPlan &pl) {
   return why;
 }
 
-bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
+bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links, const int *sort_width) {
   wh = WvHost();
   wh.why = WV_WHY_OTHER;
   const int n_c = pl.n_c, n_e = pl.n_e, m = pl.m;
@@ -133,6 +133,11 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
   const int bpr = 16 / lpb;
   std::vector<std::vector<int>> hin(nb);
   for (int e = 0; e < n_e; e++) hin[hblk[e]].push_back(e);          // elimination order = row order inside a block
+  if (sort_width) {
+    auto width = [&](int e) { const int w = sort_width[h_of[e]]; return (w > 0 && w < bs) ? w : bs; };
+    for (auto &v : hin) std::stable_sort(v.begin(), v.end(), [&](int a, int b) { return width(a) > width(b); });
+    wh.jsorted = true;
+  }
   int maxh = 0;
   for (auto &v : hin) maxh = std::max(maxh, (int)v.size());
   const int NS = std::max(1, (maxh + lpb - 1) / lpb), NV = (bs + lpb - 1) / lpb;
@@ -222,5 +227,36 @@ bool wv_plan_build(const QpPlan &pl, WvHost &wh, bool allow_links) {
   wh.per_cu = SCO_WV_PER_CU;
   const bool fits = wh.lds_bytes <= 40 * 1024;
   wh.why = fits ? WV_OK : WV_WHY_LDS;
+  wv_plan_widths(wh, nullptr, false);       // no hint: every slot at the full width, the generic kernel
   return fits;
+}
+
+// Jacobian widths of the hinge slots from the caller's hint, and the compiled profile that covers them (layout_wv.h).
+// Nothing else of the plan changes: the rows stay on their lanes and slots, so a block's partial column sums add in the
+// order they did.
+void wv_plan_widths(WvHost &wh, const int *row_width, bool off) {
+  const WvTab T = wv_tab_layout(wh.NS, wh.NV, wh.NL);
+  wh.jw_profile = 0;
+  for (int q = 0; q < WV_MAXNS; q++) wh.jw[q] = 0;
+  if (wh.tab.size() < (size_t)T.total * 64) return;                 // (a refused pattern: no tables)
+  for (int q = 0; q < wh.NS && q < WV_MAXNS; q++)
+    for (int l = 0; l < 64; l++) {
+      const int h = wh.tab[(size_t)(T.hrow + q) * 64 + l];
+      if (h < 0) continue;
+      const int w = row_width ? row_width[h] : 0;
+      // (no promise, w <= 0, and a width of the whole block or beyond it both mean every column: bs)
+      wh.jw[q] = std::max(wh.jw[q], (w > 0 && w < wh.bs) ? w : wh.bs);
+    }
+  if (off || !row_width) return;
+  // profiles exist for <7,4,3,10,3> without link rows (wv_launch); of those that cover the widths, the one with the fewest
+  // columns; none: the generic kernel
+  if (!(wh.BS == 7 && wh.NS == 4 && wh.NSTEP == 10 && wh.lpb == 3 && !wh.NL) || !wv_jreg(wh.NS, wh.BS)) return;
+  int best = 0, best_cols = 4 * wh.BS;
+#define X(a, b, c, d) \
+  if (wh.jw[0] <= (a) && wh.jw[1] <= (b) && wh.jw[2] <= (c) && wh.jw[3] <= (d) && (a) + (b) + (c) + (d) < best_cols) { \
+    best = WV_JW_PACK(a, b, c, d); best_cols = (a) + (b) + (c) + (d); \
+  }
+  WV_JW_PROFILES(X)
+#undef X
+  wh.jw_profile = best;
 }

@@ -382,7 +382,59 @@ static int sweep(const Pat &p) {
   return 0;
 }
 
+// The Jacobian width hint on the penalty QP of a descriptor (sqp_row_widths -> wv_plan_widths): for link points on the
+// given links, the widths stay inside [0, bs], the profile covers them or is the generic one, the switch forces the generic
+// one, a hint of any kind leaves every other field and table of the plan alone, and hints with entries out of range (0,
+// negative, beyond bs) promise nothing.
+static long long n_hint, n_profiled;
+#ifndef SWEEP_PARENT
+static int sweep_hint(const sco_trajopt_desc &desc, const SqpLayout &L, const Pat &q1, const std::vector<int> &links) {
+  QpPlan pl;
+  if (qp_plan_build(q1.n, q1.m, q1.Pp.data(), q1.Pi.data(), q1.Ap.data(), q1.Ai.data(), 1, pl) != 0) return 0;
+  WvHost w;
+  if (!wv_plan_build(pl, w, true)) return 0;
+  Dg d0; dg_wv(d0, true, w);
+  std::vector<int> rw;
+  const bool hint = sqp_row_widths(L.point, L.S, desc.dof, desc.n_obstacles, L.R, L.NBt, L.m_lin, L.m, links.data(), rw);
+  if ((int)rw.size() != L.m) return fail(q1, 1, "hint", "row_width is not m long");
+  const bool arm = L.point == ROWS_ARM || L.point == ROWS_SPATIAL;
+  if (hint != arm) return fail(q1, 1, "hint", "hint for a family without the guarantee, or none for one with it");
+  for (int variant = 0; variant < 4; variant++) {
+    std::vector<int> h = rw;
+    if (variant == 2) for (size_t i = 0; i < h.size(); i += 3) h[i] = -5;               // promises withdrawn row by row
+    if (variant == 3) for (size_t i = 0; i < h.size(); i += 2) h[i] = 1000;             // widths beyond the block
+    wv_plan_widths(w, hint ? h.data() : nullptr, variant == 1);
+    n_hint++;
+    for (int q = 0; q < WV_MAXNS; q++) if (w.jw[q] < 0 || w.jw[q] > w.bs || (q >= w.NS && w.jw[q])) return fail(q1, 1, "hint", "width out of range");
+    if (w.jw_profile) {
+      n_profiled++;
+      if (variant == 1 || !hint) return fail(q1, 1, "hint", "a profile with the switch off or without a hint");
+      if (!(w.BS == 7 && w.NS == 4 && w.NSTEP == 10 && w.lpb == 3 && !w.NL)) return fail(q1, 1, "hint", "a profile on a plan without profiled kernels");
+      for (int q = 0; q < 4; q++) if (wv_jw(w.jw_profile, q, w.BS) < w.jw[q] || wv_jw(w.jw_profile, q, w.BS) > w.BS) return fail(q1, 1, "hint", "profile does not cover the widths");
+    }
+    Dg d1; dg_wv(d1, true, w);
+    if (d1.h != d0.h) return fail(q1, 1, "hint", "the hint moved the plan");
+    // the same hint as sort_width: the rows dealt by width -- same shape and LDS request, every index in range, the same rows
+    WvHost ws;
+    if (!wv_plan_build(pl, ws, true, hint ? h.data() : nullptr)) return fail(q1, 1, "hint", "sort_width refused an accepted pattern");
+    if (const char *e = ck_wv(pl, ws)) return fail(q1, 1, "hint sorted", e);
+    if (ws.tab.size() != w.tab.size() || ws.lds_bytes != w.lds_bytes || ws.BS != w.BS || ws.NS != w.NS || ws.NV != w.NV || ws.NSTEP != w.NSTEP || ws.lpb != w.lpb)
+      return fail(q1, 1, "hint", "sort_width changed the shape of the plan");
+    const WvTab T = wv_tab_layout(w.NS, w.NV, w.NL);
+    std::vector<int> ra, rb;
+    for (int q = 0; q < w.NS; q++) for (int l = 0; l < 64; l++) { ra.push_back(w.tab[(size_t)(T.hrow + q) * 64 + l]); rb.push_back(ws.tab[(size_t)(T.hrow + q) * 64 + l]); }
+    std::sort(ra.begin(), ra.end()); std::sort(rb.begin(), rb.end());
+    if (ra != rb) return fail(q1, 1, "hint", "sort_width lost or doubled a hinge row");
+    wv_plan_widths(ws, hint ? h.data() : nullptr, false);
+    for (int q = 1; q < ws.NS; q++) if (ws.jw[q] > ws.jw[q - 1]) return fail(q1, 1, "hint", "sorted widths do not fall from slot to slot");
+  }
+  return 0;
+}
+#endif
+
+static const char *only_tag;      // argv[2]: sweep only the descriptors of this tag (a quick partial run; no coverage verdict)
 static int sweep_desc(const sco_trajopt_desc &desc, const char *tag) {
+  if (only_tag && strcmp(only_tag, tag)) return 0;
   const char *err = nullptr;
   if (sqp_check_desc(&desc, 0, nullptr, nullptr, nullptr, &err) != SCO_OK) return 0;
   const SqpLayout L = sqp_layout_build(desc, 0, nullptr, nullptr, nullptr);
@@ -391,6 +443,15 @@ static int sweep_desc(const sco_trajopt_desc &desc, const char *tag) {
   if (sweep(from_qp(std::string(label) + ":qp0", L.qp0, L.n_x, L.m_lin + L.n_x))) return 1;
   const Pat q1 = from_qp(std::string(label) + ":qp1", L.qp1, L.n, L.m);
   if (sweep(q1)) return 1;
+#ifndef SWEEP_PARENT
+  {
+    // link points spread over the links, all on the first, all on the last, and in descending order
+    const int K = desc.n_points, d = desc.dof;
+    std::vector<int> spread(K), first(K, 0), last(K, d - 1), down(K);
+    for (int k = 0; k < K; k++) { spread[k] = std::min(d - 1, ((k + 1) * d - 1) / K); down[k] = std::max(0, d - 1 - k); }
+    for (const auto &links : {spread, first, last, down}) if (sweep_hint(desc, L, q1, links)) return 1;
+  }
+#endif
   // rows the wavefront tier refuses for a reason of its own, added to the penalty QP of the plain descriptors
   if ((desc.family & ~15) == 0 && desc.dof >= 2 && desc.dof <= 3 && desc.horizon >= 4 && desc.horizon <= 5) {
     const int d = desc.dof;
@@ -407,6 +468,7 @@ static int sweep_desc(const sco_trajopt_desc &desc, const char *tag) {
 int main(int argc, char **argv) {
   out = argc > 1 ? fopen(argv[1], "w") : stdout;
   if (!out) { printf("cannot write %s\n", argv[1]); return 1; }
+  only_tag = argc > 2 ? argv[2] : nullptr;
   // ---- trajectory descriptors
   const int horizons[] = {2, 3, 5, 9, 10, 17, 18, 21, 22, 24};
   const int fams[] = {SCO_FAM_ARM_CIRCLES, SCO_FAM_ARM_REACH, SCO_FAM_POINT_CIRCLES, SCO_FAM_STATE_QUADRATIC, SCO_FAM_STATE_PROGRAM};
@@ -421,6 +483,13 @@ int main(int argc, char **argv) {
             const sco_trajopt_desc desc = {3, dof, T, fam <= SCO_FAM_ARM_REACH ? 2 : 1, 2, family, 0, 0, var == 2 ? 2 : 0, var == 1 ? 1 : 0};
             if (sweep_desc(desc, "traj")) return 1;
           }
+  // ---- descriptors with a Jacobian width hint that reaches a profiled kernel: 7 joints, 17 .. 20 timesteps, 5 link points,
+  // two obstacles, planar and spatial (the other descriptors of the sweep take the hint too, and stay generic)
+  for (int fam : {SCO_FAM_ARM_CIRCLES, SCO_FAM_ARM_REACH, SCO_FAM_ARM_SPATIAL})
+    for (int T = 16; T <= 21; T++) {
+      const sco_trajopt_desc desc = {3, 7, T, 5, 2, fam, 0, 0, 0, 0};
+      if (sweep_desc(desc, "hint")) return 1;
+    }
   // ---- wide descriptors: block orders 12 and 16 of the structured form; 12 x 50 is beyond a CU's LDS without force_big
   // ... and a long narrow one (2 x 50, 10 obstacles): 500 slacks beside a core of 100 leave too few threads for the free rows
   // in two row slots, on a W tile that has no three-slot kernel (rl_plan_build refuses; the tier choice goes on)
@@ -436,7 +505,7 @@ int main(int argc, char **argv) {
   // every eighth one banded (the structured form takes those), every 500th larger than the on-chip planners' caps
   unsigned long long rng = 88172645463325252ull;
   auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (unsigned)(rng >> 11); };
-  for (int it = 0; it < 3000; it++) {
+  for (int it = 0; it < (only_tag ? 0 : 3000); it++) {
     const bool large = it % 500 == 499, banded = it % 8 == 0;
     Pat p;
     p.n = large ? 520 + next() % 600 : 2 + next() % 60; p.m = large ? 1100 + next() % 2200 : next() % 120;
@@ -478,6 +547,11 @@ int main(int argc, char **argv) {
     if (!n_why[w]) covered = false;
   }
   printf("qp_choose_tiers: SCO_OK %lld  SCO_ERR_ARG %lld  SCO_ERR_CAPACITY %lld\n", n_tier_rc[0], n_tier_rc[-SCO_ERR_ARG], n_tier_rc[-SCO_ERR_CAPACITY]);
+  printf("width hints: %lld applied, %lld with a profile\n", n_hint, n_profiled);
+#ifndef SWEEP_PARENT
+  if (!n_hint || !n_profiled) covered = false;
+#endif
+  if (only_tag) { printf("partial sweep (%s): every accepted plan of it keeps its indices in range\n", only_tag); return 0; }
   if (!covered) { printf("COVERAGE: a planner, a block order or a WvWhy code did not appear\n"); return 1; }
   printf("every accepted plan keeps its indices in range and its LDS request within its planner's cap\n");
   return 0;
